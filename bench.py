@@ -13,6 +13,14 @@ videos rendered on the host once (data="synthetic").
     python bench.py [--gpus N --steps K --warmup W]     (N > 1: starts N ranks itself)
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds everything else the line can hold, each of which takes runs of its own:
+the per-kernel roofline probes (eager steps after the timed region), the
+BASELINE configs #2-#5 as extra timed legs and the CPU baseline; --legs,
+--cpu_baseline and --probe_steps choose among them under --full.
+--dump-outputs DIR writes what the last timed step computed (loss, frames,
+positions, updated parameters, gradients) as DIR/<name>.npy.
+
 --gpus must equal the launcher's WORLD_SIZE when one is set (else exit 2).
 
 Weak scaling: B sequences per rank.  Rank 0 prints ONE JSON line.
@@ -100,13 +108,19 @@ def parse():
     ap.add_argument("--ae", type=float, default=3.0)
     ap.add_argument("--lr", type=float, default=6e-4)
     ap.add_argument("--dataset", type=int, default=8, help="resident dataset size in batches (one epoch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: roofline probes, the legs of "
+                         "BASELINE configs #2-#5, the CPU baseline (see --probe_steps, --legs, --cpu_baseline)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last of them computed as DIR/<name>.npy "
+                         "(fp32 / fp64; arrays over 2^20 elements as a fixed seeded sample; rank 0)")
     ap.add_argument("--probe", default="auto", help="kernel tag of the roofline object (auto: the longest "
                     "launch of the family of the top kernel in the newest committed profiles/rNN_summary_graph.txt)")
     ap.add_argument("--traffic", default=None,
                     help="committed rocprofv3 FETCH_SIZE/WRITE_SIZE summary (tools/pmc_traffic.py)")
     ap.add_argument("--graph", type=int, default=1, help="capture fwd+loss+bwd in a HIP graph (the batch "
                     "gather is launched eagerly before each replay)")
-    ap.add_argument("--probe_steps", type=int, default=5, help="eager steps timing the probed kernel")
+    ap.add_argument("--probe_steps", type=int, default=5, help="eager steps timing the probed kernel (--full)")
     ap.add_argument("--graph_optimizer", type=int, default=1,
                     help="at N=1 capture the RMSprop launch in the step graph too (it runs every replay; "
                          "no all-reduce to order it after, no step counter in RMSprop)")
@@ -121,14 +135,19 @@ def parse():
                     help="U-Net conv arithmetic: split = f16/bf16 hi+lo operands on the 16-bit matrix cores, "
                          "fp32-accurate (meets the 1e-4 parity bar; default); fp32 = f32-input MFMA; "
                          "bf16 = bf16 operands (config #2)")
-    ap.add_argument("--legs", type=int, default=1, help="also time BASELINE configs #2-#5 (LEGS) in the same line")
+    ap.add_argument("--legs", type=int, default=1, help="with --full: also time BASELINE configs #2-#5 (LEGS) in the same line")
     ap.add_argument("--leg_steps", type=int, default=10)
     ap.add_argument("--leg_warmup", type=int, default=3)
     ap.add_argument("--leg_render", type=int, default=64,
                     help="distinct synthetic sequences rendered per leg (tiled to the resident dataset)")
-    ap.add_argument("--cpu_baseline", type=int, default=1)
+    ap.add_argument("--cpu_baseline", type=int, default=1, help="with --full: time the oracle on this host's CPUs")
     ap.add_argument("--cpu_seconds", type=float, default=10.0, help="CPU time budget per cpu_baseline sample")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:
+        a.legs = a.cpu_baseline = a.probe_steps = 0
+    return a
 
 
 def host_cores():
@@ -220,9 +239,46 @@ TASKS = {"spring_color": ("spring_ode_cell", 4, 6, 32), "spring_color_half": ("s
          "mnist_spring_color": ("spring_ode_cell", 3, 7, 64)}
 
 
-def run_workload(a, world, rank, dev, task, batch, seq_len, conv_math, steps, warmup, probe_steps, n_render):
+DUMP_SAMPLE = 1 << 20     # elements kept of a larger dumped array
+DUMP_LIMIT = 64 << 20     # bytes, all dumped arrays together
+
+
+def step_outputs(m, loss):
+    """What a caller of the train step holds after it: the losses, the decoded
+    frames and positions of the forward, every updated parameter and its
+    gradient."""
+    out = {"loss": loss, "extrap_loss": m.extrap_loss, "recons_loss": m.recons_loss, "output_seq": m.output,
+           "recons_out": m.recons_out, "enc_pos": m.enc_pos, "pos_vel_seq": m.pos_vel_seq}
+    for n, p in m.named_parameters():
+        out["param." + n] = p.data
+        if p.grad is not None:
+            out["grad." + n] = p.grad
+    return out
+
+
+def dump_outputs(path, tensors):
+    """DIR/<name>.npy per tensor, fp32 (fp64 stays fp64); an array over
+    DUMP_SAMPLE elements is written as the same seeded sample of its
+    flattened elements in every run."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in tensors.items():
+        v = t.detach().to("cpu").numpy()
+        v = np.asarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32, order="C")
+        if v.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, DUMP_SAMPLE, replace=False))
+            v = v.reshape(-1)[idx]
+        total += v.nbytes
+        if total > DUMP_LIMIT:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_LIMIT} bytes at {name}")
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
+def run_workload(a, world, rank, dev, task, batch, seq_len, conv_math, steps, warmup, probe_steps, n_render,
+                 dump=None):
     """One timed training workload: returns seqs/s over all ranks, the step
-    time, the final loss, the per-kernel probe summaries and the dataset."""
+    time, the final loss, the per-kernel probe summaries and the dataset.
+    dump: a directory for the last timed step's outputs (dump_outputs)."""
     from paig_reproduction_amd.nn.datasets.synth import render_sequences
     from paig_reproduction_amd.nn.network.physics_models import PhysicsNet
     from paig_reproduction_amd.nn.datasets.iterators import DeviceDataIterator
@@ -290,14 +346,18 @@ def run_workload(a, world, rank, dev, task, batch, seq_len, conv_math, steps, wa
     per = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(steps))
     med_ms = per[len(per) // 2] if len(per) % 2 else 0.5 * (per[len(per) // 2 - 1] + per[len(per) // 2])
     lossv = float(loss.item())
+    if dump:
+        dump_outputs(dump, step_outputs(m, loss))
     # roofline probes: every tagged main-stream launch timed with HIP events
     # on its stream, over eager steps of the same workload after the timed region
-    probe = E.KernelProbe(None)
-    eng.probe = probe
-    for i in range(probe_steps):
-        eager_step()
-    eng.probe = None
-    kds = probe.summaries()
+    kds = {}
+    if probe_steps > 0:
+        probe = E.KernelProbe(None)
+        eng.probe = probe
+        for i in range(probe_steps):
+            eager_step()
+        eng.probe = None
+        kds = probe.summaries()
     res = {"value": world * batch * steps / el, "el": el, "med_ms": med_ms, "loss": lossv, "kds": kds, "split": gstep.split,
            "opt_in_graph": gstep.opt_in_graph, "byte_targets": eng.byte_targets is not None, "dataset_seqs": int(u8.shape[0]), "ins": ins, "pred": pred, "size": size,
            "u8_head": u8[:100]}
@@ -438,11 +498,12 @@ def main():
     dev = torch.device(f"cuda:{local}")
 
     r = run_workload(a, world, rank, dev, a.task, a.batch, a.seq_len, a.conv_math, a.steps, a.warmup, a.probe_steps,
-                     2 * a.batch)
+                     2 * a.batch, dump=a.dump_outputs if rank == 0 else None)
     el, kds = r["el"], r["kds"]
     ins, pred, size = r["ins"], r["pred"], r["size"]
     value = r["value"]
-    top_kernel, top_src = summary_top()
+    # everything from here to the line is --full's (a plain run has no probes, legs or CPU baseline)
+    top_kernel, top_src = summary_top() if a.full else (None, None)
     fam = tag_family(top_kernel)
     if a.probe != "auto":
         tag = a.probe
@@ -453,7 +514,7 @@ def main():
     roof = None
     traffic_path = a.traffic or default_traffic()
     traffic, step_bytes = pmc_traffic(traffic_path, tag, {"task": a.task, "batch": a.batch, "seq_len": a.seq_len,
-                                                           "conv_math": a.conv_math})
+                                                           "conv_math": a.conv_math}) if a.full else (None, None)
     if tag in kds:
         roof = roof_of(kds[tag], a.conv_math)
         roof.update({"traffic": round(traffic) if traffic else None, "traffic_unit": "bytes/launch (PMC)",
@@ -497,7 +558,7 @@ def main():
             "value": round(value, 2), "unit": "video-seqs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(el / a.steps * 1e3, 3), "ms_per_step_median": round(r["med_ms"], 4),
             "value_median": round(world * a.batch / (r["med_ms"] * 1e-3), 2),
-            "higher_is_better": True, "scaling": "weak",
+            "higher_is_better": True, "scaling": "weak", "full": bool(a.full),
             "vs_baseline": None, "dtype": "bf16" if a.conv_math == "bf16" else "fp32",
             "data": "synthetic",
             "config": {"workload": f"{a.task} PhysicsNet train step (get_batch gather+fwd+loss+bwd+allreduce+RMSprop), "
