@@ -31,7 +31,7 @@ extern "C" {
 /* Version of this interface: bumped whenever an entry point's argument list
  * or a data layout it exchanges changes (the Python binding refuses a library
  * of another version). */
-#define PAIG_ABI_VERSION 8
+#define PAIG_ABI_VERSION 9
 const char* paig_last_error(void);
 int paig_abi_version(void);
 /* f16 range guard of the split-precision path.  Activations and gradients
@@ -615,6 +615,29 @@ int paig_gather_u8_f32(const unsigned char* src, const long long* idx, float* ou
  * device int64[B]) receives idx[0:B] for the decoders' byte targets */
 int paig_gather_u8_f32_ex(const unsigned char* src, const long long* idx, float* out, int B, long long row,
                           long long head, long long* idx_out, void* stream);
+
+/* ---- synthetic datasets rendered on the device (nn/datasets/synth.py; no
+ *      reference counterpart: the reference ships no data and its generators
+ *      run on the host, nn/datasets/generators.py:243-364)
+ * paig_synth_integrate: m candidate trajectories from the initial states
+ * p0 / v0 (fp64 [m, K, 2], (x, y) in pixels), one lane each, fp64, in the
+ * update order of synth.py's integrators.  phys 0 spring (c0 = k, c1 = equil;
+ * K = 2), 1 bounce (K = 2), 2 gravity (c0 = g; K = 3).  pos: fp64 [m, T, K, 2],
+ * the state before each step's `sub` substeps of dt / sub.  valid[i] is the
+ * host's acceptance rule: spring, the state after every step (the last
+ * included) within [radius, size - radius]; gravity, every recorded position
+ * strictly inside; bounce, always 1. */
+int paig_synth_integrate(int phys, const double* p0, const double* v0, long long m, int K, int T, int sub, double dt,
+                         double size, double radius, double c0, double c1, double* pos, int* valid, void* stream);
+/* paig_synth_raster: out = uint8 [n, T, size, size, 3] (NHWC, the npz
+ * layout; size a multiple of 4), bit for bit the frames of
+ * synth.render_sequences for the same positions: disks of `radius` with 4 x 4
+ * subsamples per pixel, object j on channel 2 - j % 3.  Sequence i draws
+ * trajectory rows[i] of pos (rows: device int64 [n], nullable = i).  bg
+ * (nullable): fp32 [n, size, size], a per-sequence background shared by the
+ * three channels (byte = uint8(clip(max(bg, cover), 0, 1) * 255)). */
+int paig_synth_raster(const double* pos, const long long* rows, long long n, int T, int K, int size, double radius,
+                      const float* bg, unsigned char* out, void* stream);
 
 /* ---- optimizers over the flat parameter buffer (base.py:12-17, torch defaults) */
 int paig_rmsprop_f32(float* p, const float* g, float* sa, long long n, float lr, float alpha, float eps, void* stream);

@@ -17,7 +17,7 @@ XMAX_SLOTS = 2048
 
 AB_PATH = os.environ.get("PAIG_AB_LIB")
 # include/paig_hip.h PAIG_ABI_VERSION: the SIGNATURES below are this version's
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -136,6 +136,8 @@ SIGNATURES = {
     "paig_loss_bwd": (I, [P, P, P, F32, P, P, I, I, I, I, P]),
     "paig_frame_sse": (I, [P, LL, I, LL, P, LL, I, LL, P, I, I, P]),
     "paig_frame_sse_bwd": (I, [P, LL, I, LL, P, LL, I, LL, P, P, I, I, P]),
+    "paig_synth_integrate": (I, [I, P, P, LL, I, I, I, F64, F64, F64, F64, F64, P, P, P]),
+    "paig_synth_raster": (I, [P, P, LL, I, I, I, F64, P, P, P]),
     "paig_rmsprop_f32": (I, [P, P, P, LL, F32, F32, F32, P]),
     "paig_rmsprop_f64": (I, [P, P, P, LL, F64, F64, F64, P]),
     "paig_rmsprop_mixed": (I, [P, P, P, LL, P, P, P, LL, F64, F64, F64, P]),

@@ -94,7 +94,14 @@ class DeviceDataIterator(DataIterator):
         self.device = torch.device(device)
         self.idx_d = None
         self.bound = None
-        super().__init__(torch.from_numpy(np.ascontiguousarray(X_u8)).to(self.device), None, seed, rank, world)
+        if torch.is_tensor(X_u8):
+            # a dataset produced on the device (synth_device.py): used as is
+            assert X_u8.dtype == torch.uint8 and X_u8.is_contiguous() and X_u8.device == self.device, \
+                (X_u8.dtype, X_u8.device, self.device)
+            X = X_u8
+        else:
+            X = torch.from_numpy(np.ascontiguousarray(X_u8)).to(self.device)
+        super().__init__(X, None, seed, rank, world)
 
     def reset_iteration(self):
         import torch

@@ -14,6 +14,11 @@ Additive flags only:
   --seed S                       shared shuffle seed (required for DDP sharding).
   --device_data {1,0}            1 (default): uint8 dataset resident in HBM, each
         batch gathered on the GPU; 0: the reference's host path.
+  --synthetic_device {0,1}       1: with --synthetic N and the task's npz missing,
+        render the data on the GPU instead (nn/datasets/synth_device.py: HIP
+        integrators + rasteriser) and keep it in HBM; no npz is written.  Same
+        distribution as synth.py, other sequences.  Under data parallelism every
+        rank renders the same dataset and takes its shard.  0 (default): as before.
 
 Data-parallel training: launch with torchrun (one process per GPU, RCCL);
 --batch_size is per rank, every rank draws a disjoint shard of each epoch.
@@ -95,6 +100,8 @@ def build_parser():
                    help="override the conv/GEMM arithmetic directly (fp32 = f32-input MFMA)")
     p.add_argument("--device_data", type=int, default=1,
                    help="1: dataset resident in HBM as uint8, batches gathered on the GPU (F2); 0: host iterators")
+    p.add_argument("--synthetic_device", type=int, choices=(0, 1), default=0,
+                   help="1: render a missing --synthetic dataset on the GPU and keep it there (no npz written)")
     return p
 
 
@@ -113,6 +120,17 @@ def dataset_path(args, rel, seq_len):
 
 def _rank():
     return dist.get_rank() if dist.is_initialized() else 0
+
+
+def iterators(args, rel, seq_len, rank, world, device):
+    """The task's train / valid / test iterators for sequences of seq_len."""
+    if args.synthetic_device and args.synthetic > 0 and not os.path.exists(os.path.join(args.data_dir, rel)):
+        from paig_reproduction_amd.nn.datasets.synth_device import device_iterators
+        n = args.synthetic
+        return device_iterators(args.task, seq_len, n, max(n // 10, 1), max(n // 10, 1), args.seed, device,
+                                rank=rank, world=world, data_seed=0)
+    return get_iterators(dataset_path(args, rel, seq_len), conv=True, datapoints=args.datapoints,
+                         seed=args.seed, rank=rank, world=world, device=device if args.device_data else None)
 
 
 def main(argv=None):
@@ -157,8 +175,7 @@ def main(argv=None):
 
     if not args.test_mode:
         network = make(seq_len)
-        its = get_iterators(dataset_path(args, data_file, seq_len), conv=True, datapoints=args.datapoints,
-                            seed=args.seed, rank=rank, world=world, device=device if args.device_data else None)
+        its = iterators(args, data_file, seq_len, rank, world, device)
         network.get_data(its)
         network.build_optimizer(args.base_lr, args.optimizer, args.anneal_lr)
         network.initialize_graph(args.save_dir, args.use_ckpt, args.ckpt_dir)
@@ -168,8 +185,7 @@ def main(argv=None):
     network = make(test_seq_len)
     network.build_optimizer(args.base_lr, args.optimizer, args.anneal_lr)
     network.initialize_graph(args.save_dir, True, args.ckpt_dir)
-    its = get_iterators(dataset_path(args, test_data_file, test_seq_len), conv=True, datapoints=args.datapoints,
-                        seed=args.seed, rank=rank, world=world, device=device if args.device_data else None)
+    its = iterators(args, test_data_file, test_seq_len, rank, world, device)
     network.get_data(its)
     network.train_model(0, args.batch_size, args.save_every_n_epochs, args.eval_every_n_epochs,
                         args.print_interval, args.debug)
