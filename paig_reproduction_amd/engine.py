@@ -190,6 +190,7 @@ class Engine:
         self.L = lib()
         self.probe = None
         self.last_masked_objs = None
+        self.last_loss_handoff = None   # the last forward's loss-weight hand-off (physics_models._LossHandoff)
         self._side = None   # second stream (see _fork)
         # called once per backward when the early gradient bucket is final
         # (FlatParams.allreduce_early by default; bench.py splits its HIP graph here)

@@ -44,8 +44,47 @@ COORD_UNITS = {
 }
 
 
+class _LossHandoff:
+    """What the _LossReduce backwards of ONE forward leave for that forward's
+    _PhysicsStep.backward: per SSE output (reconstruction / rollout frames) a
+    list of (in_kernel, (dt, de, dr, ae, B, Te, R, pred)), one entry per
+    compute_loss() whose loss reached the backward.  It lives on the forward's
+    autograd context, so another model, another forward or an earlier backward
+    can neither overwrite nor outlive it."""
+    __slots__ = ("rec", "roll")
+
+    def __init__(self):
+        self.rec, self.roll = [], []
+
+    def take(self):
+        out = (self.rec[:], self.roll[:])
+        del self.rec[:], self.roll[:]
+        return out
+
+
+def _materialise_lossw(entries, mode, dev):
+    """The per-frame weights of in-kernel hand-off entries as an array (the
+    rare paths: several losses on one forward, or a user gradient on the
+    public SSE as well): one paig_loss_bwd per entry, summed."""
+    w = None
+    for _, (dt, de, dr, ae, B, Te, R, pred) in entries:
+        wi = torch.empty(B * (Te if mode == 1 else R), device=dev)
+        lib().paig_loss_bwd(ptr(dt), ptr(de), ptr(dr), ae, ptr(wi) if mode == 1 else None,
+                            ptr(wi) if mode == 2 else None, B, Te, R, pred, stream_handle(dev))
+        w = wi if w is None else w + wi
+    return w
+
+
 class _PhysicsStep(torch.autograd.Function):
-    """The whole forward as one node; backward = engine.backward."""
+    """The whole forward as one node; backward = engine.backward.
+
+    The per-frame SSE leaves it twice: sse_rec / sse_roll are the public
+    tensors (PhysicsNet._sse_rec / _sse_roll; a gradient arriving there is an
+    ordinary array of values), priv_rec / priv_roll alias the same memory and
+    are consumed by compute_loss alone.  Only _LossReduce.backward ever
+    returns a gradient for the private pair, and it says what that gradient
+    means through the forward's _LossHandoff, so a NaN stand-in never meets a
+    user gradient."""
 
     @staticmethod
     def forward(ctx, anchor, x, engine):
@@ -53,41 +92,62 @@ class _PhysicsStep(torch.autograd.Function):
         res, S = engine.forward(x, need_saved=need)
         ctx.engine = engine
         ctx.S = S
+        ctx.hand = engine.last_loss_handoff = _LossHandoff()
         ctx.set_materialize_grads(False)
         engine.last_masked_objs = res["masked_objs"]
         outs = (res["output_seq"], res["recons_out"], res["enc_pos"], res["pos_vel_seq"], res["sse_rec"],
-                res["sse_roll"], res["enc_masks"], res["template"], res["contents"], res["background_content"])
+                res["sse_roll"], res["sse_rec"].detach(), res["sse_roll"].detach(), res["enc_masks"], res["template"],
+                res["contents"], res["background_content"])
         ctx.mark_non_differentiable(res["enc_masks"], res["template"], res["contents"], res["background_content"])
         return outs
 
     @staticmethod
-    def backward(ctx, d_out, d_rec, d_enc, d_pvs, d_sse_rec, d_sse_roll, *unused):
+    def _weights(pub, priv, entries, mode):
+        """One SSE output's incoming gradients -> (weight array or None,
+        in-kernel loss weights (mode, adjoints) or None)."""
+        if not entries:
+            return pub, None
+        kinds = {e[0] for e in entries}
+        if len(kinds) > 1:
+            raise RuntimeError("PhysicsNet: loss-weight modes mixed within one backward")
+        if kinds == {True}:
+            if len(entries) == 1 and pub is None:
+                return None, (mode, entries[0][1])
+            # the private gradient is a (sum of) NaN stand-ins: form the values
+            w = _materialise_lossw(entries, mode, priv.device)
+        else:
+            w = priv   # the weight arrays themselves, summed by autograd
+        return (w if pub is None else w + pub), None
+
+    @staticmethod
+    def backward(ctx, d_out, d_rec, d_enc, d_pvs, d_sse_rec, d_sse_roll, d_priv_rec, d_priv_roll, *unused):
         if ctx.S is None:
             raise RuntimeError("PhysicsNet step was run without saving activations")
+        ent_rec, ent_roll = ctx.hand.take()
         flat = ctx.engine.model._flat
         acc = flat.begin_backward()
-        # the live-steps mark of _LossReduce.backward holds only while the
-        # gradient tensor is unmodified: autograd may accumulate a second
-        # gradient path into it in place (InputBuffer's add_), which keeps the
-        # tensor (and the attribute) but bumps its version counter
-        mark = getattr(d_sse_roll, "_paig_live_steps", None) if d_out is None else None
-        live = mark[0] if mark is not None and d_sse_roll._version == mark[1] else 0
-        # in-kernel loss weights (_LossReduce.backward): only for the unmodified stand-ins
-        lw = {}
-        for key, g in (("rec", d_sse_rec), ("roll", d_sse_roll)):
-            m = getattr(g, "_paig_lossw", None)
-            if m is not None and g._version == m[2]:
-                lw[key] = m[:2]
+        # no extrapolation loss in the graph: only the first pred steps of
+        # every sequence carry a weight (physics_models.py:129-139), so the
+        # rollout decoder backward walks those frames only.  Decided afresh in
+        # every backward from what reached THIS forward: every loss on its
+        # rollout SSE came through compute_loss without an extrapolation
+        # adjoint, and nothing else (public SSE, dense frames) has a gradient.
+        live = 0
+        if d_out is None and d_sse_roll is None and ent_roll and all(lw[1] is None for _, lw in ent_roll):
+            live = ent_roll[0][1][7]
+        w_rec, lw_rec = _PhysicsStep._weights(d_sse_rec, d_priv_rec, ent_rec, 1)
+        w_roll, lw_roll = _PhysicsStep._weights(d_sse_roll, d_priv_roll, ent_roll, 2)
         # incoming gradients may be broadcast views (d sum(sse)/d sse is an
         # expanded scalar, stride 0): the kernels read dense vectors
-        d_sse_rec = d_sse_rec.contiguous() if d_sse_rec is not None else None
-        d_sse_roll = d_sse_roll.contiguous() if d_sse_roll is not None else None
-        ctx.engine.backward(ctx.S, d_sse_rec, d_sse_roll, d_out, d_rec, d_enc, d_pvs, roll_live=live, lossw=lw)
+        w_rec = w_rec.contiguous() if w_rec is not None else None
+        w_roll = w_roll.contiguous() if w_roll is not None else None
+        lw = {k: v for k, v in (("rec", lw_rec), ("roll", lw_roll)) if v is not None}
+        ctx.engine.backward(ctx.S, w_rec, w_roll, d_out, d_rec, d_enc, d_pvs, roll_live=live, lossw=lw)
         # nothing reached the rollout branch (quirk Q1: the loss read a stale
         # output): the velocity encoder and physics parameters are not in the
         # graph, so like torch they get grad None (their flat slots hold zeros)
-        none = ctx.engine.model.ROLLOUT_PARAMS if d_out is None and d_sse_roll is None and d_pvs is None else ()
-        flat.end_backward(acc, none)
+        no_roll = d_out is None and w_roll is None and lw_roll is None and d_pvs is None
+        flat.end_backward(acc, ctx.engine.model.ROLLOUT_PARAMS if no_roll else ())
         ctx.S = None
         return None, None, None
 
@@ -98,7 +158,8 @@ _LOSSW = {}
 def _lossw_buffers(dev, n_rec, n_roll):
     """Persistent NaN-filled stand-ins for the loss-weight gradients (one pair
     per device and size; filled once, outside any graph capture: the first
-    training steps run eagerly)."""
+    training steps run eagerly).  They carry nothing: whoever reads one as
+    values gets NaN, never silent garbage."""
     key = (str(dev), n_rec, n_roll)
     if key not in _LOSSW:
         _LOSSW[key] = (torch.full((n_rec,), float("nan"), device=dev), torch.full((n_roll,), float("nan"), device=dev))
@@ -111,45 +172,46 @@ class _LossReduce(torch.autograd.Function):
     reference's in-place ``+=`` leaves in BOTH train_loss and pred_loss (Q2)."""
 
     @staticmethod
-    def forward(ctx, sse_rec, sse_roll, B, Te, R, pred, ae):
+    def forward(ctx, sse_rec, sse_roll, B, Te, R, pred, ae, hand_rec, hand_roll):
+        """hand_rec / hand_roll: the _LossHandoff lists of the forward whose
+        PRIVATE SSE output sse_rec / sse_roll is, or None for any other
+        tensor (its gradient is then always an array of values)."""
         dev = sse_rec.device
         o = [torch.empty((), device=dev) for _ in range(3)]
         lib().paig_loss_reduce(ptr(sse_rec), ptr(sse_roll), B, Te, R, pred, float(ae), ptr(o[0]), ptr(o[1]),
                                ptr(o[2]), stream_handle(dev))
         ctx.shape = (B, Te, R, pred, float(ae))
         ctx.dev = dev
+        ctx.hands = (hand_rec, hand_roll)
         ctx.set_materialize_grads(False)
         return o[0], o[1], o[2]
 
     @staticmethod
     def backward(ctx, dt, de, dr):
         B, Te, R, pred, ae = ctx.shape
-        if os.environ.get("PAIG_LOSSW_INKERNEL", "1") != "0" and not torch.is_grad_enabled():
-            # the per-frame weights are formed inside the decoder backwards
-            # from these adjoints (paig_decoder_bwd_ex lw modes): the returned
-            # gradients are persistent NaN buffers carrying the adjoints, so a
-            # path that reads them as values (another gradient accumulated into
-            # them) gets NaN, never silent garbage
-            wrec, wroll = _lossw_buffers(ctx.dev, B * Te, B * R)
-            lw = (dt, de, dr, ae, B, Te, R, pred)
-            wrec._paig_lossw = (1, lw, wrec._version)
-            wroll._paig_lossw = (2, lw, wroll._version)
-            if de is None:
-                wroll._paig_live_steps = (pred, wroll._version)
-            return wrec, wroll, None, None, None, None, None
-        wrec = torch.empty(B * Te, device=ctx.dev)
-        wroll = torch.empty(B * R, device=ctx.dev)
-        lib().paig_loss_bwd(ptr(dt), ptr(de), ptr(dr), ae, ptr(wrec), ptr(wroll), B, Te, R, pred,
-                            stream_handle(ctx.dev))
-        if de is None:
-            # no extrapolation loss in the graph: only the first pred steps of
-            # every sequence carry a weight (physics_models.py:129-139), so the
-            # rollout decoder backward walks those frames only.  The mark
-            # carries the tensor's version: a gradient that autograd
-            # accumulates with another one (in place or not) no longer
-            # matches it and falls back to every frame.
-            wroll._paig_live_steps = (pred, wroll._version)
-        return wrec, wroll, None, None, None, None, None
+        lw = (dt, de, dr, ae, B, Te, R, pred)
+        # in-kernel: the per-frame weights are formed inside the decoder
+        # backwards from these adjoints (paig_decoder_bwd_ex lw modes).  The
+        # adjoints travel on the forward's hand-off; the returned gradient is
+        # a persistent NaN buffer that only tells autograd the path is live.
+        inkernel = os.environ.get("PAIG_LOSSW_INKERNEL", "1") != "0" and not torch.is_grad_enabled()
+        standin = _lossw_buffers(ctx.dev, B * Te, B * R)
+        grads, arrays = [None, None], [None, None]
+        for i, hand in enumerate(ctx.hands):
+            if not ctx.needs_input_grad[i]:
+                continue
+            if i == 1 and dt is None and de is None:
+                continue   # only the reconstruction loss is in the graph: the rollout SSE gets no gradient
+            if hand is not None:
+                hand.append((inkernel, lw))
+            if hand is not None and inkernel:
+                grads[i] = standin[i]
+            else:
+                grads[i] = arrays[i] = torch.empty(B * (R if i else Te), device=ctx.dev)
+        if arrays[0] is not None or arrays[1] is not None:
+            lib().paig_loss_bwd(ptr(dt), ptr(de), ptr(dr), ae, ptr(arrays[0]), ptr(arrays[1]), B, Te, R, pred,
+                                stream_handle(ctx.dev))
+        return grads[0], grads[1], None, None, None, None, None, None, None
 
 
 class _FrameSSE(torch.autograd.Function):
@@ -308,15 +370,16 @@ class PhysicsNet(BaseNetTorch):
         """nn/network/physics_models.py:119-142, including the in-place ``+=``
         that makes pred_loss alias train_loss (Q2)."""
         B, Te, R = self.input.shape[0], self.input_steps + self.pred_steps, self.pred_steps + self.extrap_steps
-        sse_rec = self._sse_rec
+        # the forward's private SSE outputs and its loss hand-off (_PhysicsStep)
+        sse_rec, (hand_rec, hand_roll) = self._sse_priv[0], self._sse_priv[2]
         if self.output is self._fwd_output:
-            sse_roll = self._sse_roll
+            sse_roll = self._sse_priv[1]
         else:
-            sse_roll = _FrameSSE.apply(self.output, self.input, self.input_steps)
+            sse_roll, hand_roll = _FrameSSE.apply(self.output, self.input, self.input_steps), None
         # train = pred + ae * recons in one kernel; pred_loss IS train_loss, as
         # after the reference's in-place ``train_loss += ae * recons`` (Q2)
         train, extrap, recons = _LossReduce.apply(sse_rec, sse_roll, B, Te, R, self.pred_steps,
-                                                  self.autoencoder_loss)
+                                                  self.autoencoder_loss, hand_rec, hand_roll)
         self.recons_loss = recons
         self.pred_loss = train
         self.extrap_loss = extrap
@@ -467,7 +530,9 @@ class PhysicsNet(BaseNetTorch):
         if x.dtype != torch.float32:
             x = x.float()
         outs = _PhysicsStep.apply(self._anchor, x, eng)
-        (out, recons, enc_pos, pvs, sse_rec, sse_roll, masks, tmpl, cont, bg) = outs
+        (out, recons, enc_pos, pvs, sse_rec, sse_roll, priv_rec, priv_roll, masks, tmpl, cont, bg) = outs
+        hand = eng.last_loss_handoff
+        object.__setattr__(self, "_sse_priv", (priv_rec, priv_roll, (hand.rec, hand.roll)))
         self.recons_out = recons
         self.enc_pos = enc_pos
         self.pos_vel_seq = pvs

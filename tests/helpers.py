@@ -32,8 +32,28 @@ def rel_err(a, b):
     a = np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype=np.float64)
     b = np.asarray(b.detach().cpu() if torch.is_tensor(b) else b, dtype=np.float64)
     assert a.shape == b.shape, (a.shape, b.shape)
-    scale = max(np.abs(b).max(), 1e-30) if b.size else 1.0
-    return float(np.abs(a - b).max() / scale) if b.size else 0.0
+    if not b.size:
+        return 0.0
+    # a non-finite value where the reference is finite is an infinite error
+    # (np.max would give NaN, which every comparison and Python's max() drop)
+    if (~np.isfinite(a) & np.isfinite(b)).any():
+        return float("inf")
+    scale = max(np.abs(b).max(), 1e-30)
+    return float(np.abs(a - b).max() / scale)
+
+
+def worst_err(pairs):
+    """{key: (got, want)} -> (worst rel_err, its key); (0.0, None) when empty.
+    An error that is not a number (a NaN reference) counts as infinite, so no
+    ordering of the keys can hide it."""
+    worst, at = 0.0, None
+    for k, (got, want) in pairs.items():
+        e = rel_err(got, want)
+        if e != e:
+            e = float("inf")
+        if at is None or e > worst:
+            worst, at = e, k
+    return worst, at
 
 
 def assert_close(a, b, rtol=RTOL, what=""):

@@ -26,7 +26,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN_DIR, golden_weights, rel_err, grad_checks, RTOL
+from helpers import GOLDEN_DIR, golden_weights, rel_err, worst_err, grad_checks, RTOL
 from envelope import ENVELOPE_K, _ulp_perturbed
 from oracle import physics_oracle as O
 
@@ -302,14 +302,14 @@ def test_optimizer_skips_params_without_grad(kind):
         assert rel_err(named[k].grad, want) <= 1e-6, (kind, k)
 
 
-def test_rollout_sse_second_gradient_path():
+def _second_gradient_path(with_extrap):
     """the live-steps hint that lets the rollout decoder backward
     skip the frames without a loss weight (physics_models.py:129-139 weights
     loss[:, :pred_steps] only) must not survive when the per-frame SSE gets a
-    second gradient path that autograd accumulates into the same tensor:
-    every rollout frame then carries a weight.  Gradients of
-    train_loss + 0.5 * sum(sse_roll) must equal the sum of the two losses'
-    separate gradients."""
+    second gradient path next to compute_loss's: every rollout frame then
+    carries a weight.  Gradients of train_loss + 0.5 * sum(sse_roll) must
+    equal the sum of the two losses' separate gradients; with_extrap: the
+    compute_loss part is train_loss + 0.5 * extrap_loss."""
     dev = torch.device("cuda:0")
     z = _load("traj_spring_s12")
     x = _x(z["input_u8_0"], dev)
@@ -317,7 +317,9 @@ def test_rollout_sse_second_gradient_path():
     def grads(which):
         m = _model(z, dev)
         m.output = m(x)
-        loss, _ = m.compute_loss()
+        loss, (_, extrap, _) = m.compute_loss()
+        if with_extrap:
+            loss = loss + 0.5 * extrap
         extra = 0.5 * m._sse_roll.sum()
         total = {"train": loss, "sse": extra, "both": loss + extra}[which]
         total.backward()
@@ -325,13 +327,19 @@ def test_rollout_sse_second_gradient_path():
 
     ga, gb, gc = grads("train"), grads("sse"), grads("both")
     assert set(gc) == set(ga) | set(gb)
-    worst = 0.0
-    for k in gc:
-        want = ga.get(k, 0) + gb.get(k, 0)
-        worst = max(worst, rel_err(gc[k], want))
+    assert any(float(g.abs().max()) > 0 for g in gb.values())
     # the extrapolation frames' decoder gradient reaches the VFN sources: a
     # surviving mark would drop it entirely (an O(1) error)
-    assert worst <= 1e-5, worst
+    worst, key = worst_err({k: (gc[k], ga.get(k, 0) + gb.get(k, 0)) for k in gc})
+    assert worst <= 1e-5, (worst, key)
+
+
+def test_rollout_sse_second_gradient_path():
+    _second_gradient_path(False)
+
+
+def test_rollout_sse_second_gradient_path_with_extrap():
+    _second_gradient_path(True)
 
 
 def test_two_forwards_before_backward():
@@ -357,5 +365,6 @@ def test_two_forwards_before_backward():
         return {k: p.grad.detach().clone() for k, p in m.named_parameters() if p.grad is not None}
 
     ga, gb, gc = grads([x1]), grads([x2]), grads([x1, x2])
-    worst = max(rel_err(gc[k], ga[k] + gb[k]) for k in gc)
-    assert worst <= 1e-5, worst
+    assert set(gc) == set(ga) == set(gb)
+    worst, key = worst_err({k: (gc[k], ga[k] + gb[k]) for k in gc})
+    assert worst <= 1e-5, (worst, key)
