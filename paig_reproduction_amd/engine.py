@@ -20,6 +20,8 @@ memory (caching allocator), streams and the autograd hook.
 """
 import ctypes
 import os
+from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import torch
 
@@ -32,15 +34,74 @@ from ._lib import PaigError, lib, ptr, stream_handle, require_device
 # engine's U-Net stage.  Python only names the convs (c1..cN, plan order).
 
 
+class Switches(NamedTuple):
+    """The step's A/B switches (all on by default; "0" turns one off)."""
+    fuse_head: bool        # PAIG_FUSE_HEAD: the U-Net's 1x1 head inside the mask softmax (Layout.fuse_head)
+    dense_tail: bool       # PAIG_DENSE_TAIL: l2 + position head as fp32 FMA around l1 (Engine.dense_tail)
+    fuse_vfn: bool         # PAIG_FUSE_VFN: velocity MLP + VFN sources in one launch
+    merge_roll: bool       # PAIG_MERGE_ROLL: rollout + reconstruction decode in one launch
+    fused_bwd: bool        # PAIG_FUSED_BWD: the U-Net's fused layer backward
+    upt: bool              # PAIG_UPT: upsample backward folded into the conv backward
+    pool_fold: bool        # PAIG_POOL_FOLD: max-pool backward folded into the conv backward
+    wprep_merge: bool      # PAIG_WPREP_MERGE: weight prep inside the U-Net's first conv launch
+    fuse_vel: bool         # PAIG_FUSE_VEL: velocity encoder's input gradient added inside the head backward
+    fuse_vfn2: bool        # PAIG_FUSE_VFN2: VFN backward phase 2 inside the head backward's launch
+    gemm_epi_merge: bool   # PAIG_GEMM_EPI_MERGE: l2 / l1 weight-gradient epilogues ride in the next GEMM
+
+
+def read_switches():
+    """The one place the step reads its A/B switches from the environment:
+    once per forward; the backward uses its own forward's record."""
+    return Switches(*[os.environ.get("PAIG_" + f.upper(), "1") != "0" for f in Switches._fields])
+
+
+class LossAdjoints(NamedTuple):
+    """What one compute_loss() backward hands to the decoder backwards: the
+    adjoints of (train, extrap, recons), each a 0-d tensor or None, and the
+    loss's shape (physics_models._LossReduce)."""
+    dt: object
+    de: object
+    dr: object
+    ae: float
+    B: int
+    Te: int
+    R: int
+    pred: int
+
+
+def materialise(adj, mode, dev):
+    """The per-frame loss weights of one LossAdjoints as an array (mode 1:
+    the B*Te reconstruction frames, 2: the B*R rollout frames)."""
+    w = _empty(adj.B * (adj.Te if mode == 1 else adj.R), dev)
+    lib().paig_loss_bwd(ptr(adj.dt), ptr(adj.de), ptr(adj.dr), float(adj.ae), ptr(w) if mode == 1 else None,
+                        ptr(w) if mode == 2 else None, adj.B, adj.Te, adj.R, adj.pred, stream_handle(dev))
+    return w
+
+
+def live_steps(d_out, d_sse_roll, ent_roll):
+    """How many leading rollout steps of every sequence carry a loss weight
+    (the rollout decoder backward walks those frames only), or 0 for all of
+    them.  Without an extrapolation loss only the first pred steps do
+    (physics_models.py:129-139): every loss on this forward's rollout SSE came
+    through compute_loss without an extrapolation adjoint (ent_roll: the
+    hand-off's (inkernel, LossAdjoints) entries), and nothing else (dense
+    frames d_out, the public SSE's d_sse_roll) has a gradient."""
+    if d_out is None and d_sse_roll is None and ent_roll and all(adj.de is None for _, adj in ent_roll):
+        return ent_roll[0][1].pred
+    return 0
+
+
 class Layout:
     """Static shapes of one step (from the PhysicsNet config and batch)."""
 
-    def __init__(self, model, B, T, frames=None, net=None):
-        """frames=N: the encoder alone over N independent frames (the
+    def __init__(self, model, B, T, sw, frames=None, net=None):
+        """sw: the forward's Switches.
+        frames=N: the encoder alone over N independent frames (the
         standalone ConvolutionalEncoder / U-Net calls): F = N, no sequence.
         net: "unet" / "shallow_unet" to plan that U-Net whatever the frame
         size (both are built, Q8; the live one is chosen by H otherwise)."""
-        self.B, self.T = B, T
+        self.B, self.T, self.sw = B, T, sw
+        self.sequences = frames is None
         self.K = model.n_objs
         self.D = model.coord_units // 2
         self.H = model.conv_input_shape[1]
@@ -65,6 +126,8 @@ class Layout:
         self.l1_in = 3 * (self.H // 2) ** 2 if self.unet else 3 * self.H * self.H
         self.HW = self.H * self.H
         self.frame = 3 * self.HW
+        # output sizes of the VariableFromNetwork sources, in _VFN order
+        self.vfn_sizes = (self.K * self.h * self.h, self.K * 3 * self.h * self.h, 3 * self.HW)
         # the U-Net's last layer, a 1x1 head (ShallowUNet c13, 8 -> K, ReLU'd;
         # UNet c18, 16 -> K, with the objects' AvgPool2d), is fused into the
         # mask softmax (paig_head_mask_fwd_ex / _bwd_ex) in the encoder; the
@@ -74,7 +137,7 @@ class Layout:
         self.head_ci = L.paig_unet_query(self.net, self.K, 3)
         self.head_name = f"c{self.nconv}"
         self.head_flags = (1 if self.lg_relu else 0) | (2 if self.unet else 0)
-        self.fuse_head = (self.K in (2, 3) and self.HW % 4 == 0 and os.environ.get("PAIG_FUSE_HEAD", "1") != "0" and
+        self.fuse_head = (self.K in (2, 3) and self.HW % 4 == 0 and sw.fuse_head and
                           ((not self.unet and self.head_ci == 8) or (self.unet and self.head_ci == 16 and
                                                                      self.H % 4 == 0)))
         if self.fuse_head:
@@ -88,8 +151,7 @@ class Layout:
 
 class KernelProbe:
     """Times every launch of one tagged kernel (``tag``), or of every tagged
-    kernel (``tag=None``), with HIP events recorded on the stream it is
-    launched on: the main stream; the side-stream chains are not tagged
+    kernel (``tag=None``), with HIP events recorded on the step's stream
     (bench.py's roofline numbers)."""
 
     backlog_cycles = 1 << 20
@@ -182,6 +244,67 @@ def _empty(n, device, dtype=torch.float32):
     return torch.empty(n, device=device, dtype=dtype)
 
 
+# the VariableFromNetwork sources, in the order of every paig_vfn_*_multi array
+_VFN = ("var_net_template", "var_net_content", "var_net_background")
+# the head backward's arguments when it carries no velocity term / no VFN phase 2
+_NO_VEL = (None, None, 0, 0, 0, 0)
+_NO_VFN2 = (0,) + (None,) * 11
+
+
+@dataclass(slots=True, eq=False)
+class StepState:
+    """What one forward saves for its backward (Engine.new_state is the only
+    constructor).  Every field is declared here: a misspelt one raises."""
+    lay: Layout = None          # new_state; every stage
+    x: object = None            # new_state: the input (x_view and tgt_roll point into it)
+    ws: object = None           # new_state: GEMM workspace of the dense layers; forward and backward
+    dev: object = None          # new_state; every stage
+    cm: int = 0                 # new_state: conv arithmetic flags; _unet_forward, _unet_grad, _unet_backward
+    need_saved: bool = True     # new_state: a backward may follow; _unet_forward (else the inference workspace)
+    sw: Switches = None         # new_state: the forward's A/B switches; every stage
+    x_view: tuple = None        # new_state: the encoder's frames (pointer, stride, group, group stride)
+    tb: int = 0                 # forward: 1 = the rollout targets are dataset bytes; backward
+    tgt_roll: tuple = None      # forward: the rollout decoders' target view; backward
+    src: dict = None            # forward: VFN buffers {name: (hidden, raw, post-sigmoid or None)}; backward
+    Xv: object = None           # forward: velocity encoder input rows; backward
+    v1: object = None           # forward: velocity MLP hidden 1; backward
+    v2: object = None           # forward: velocity MLP hidden 2; backward
+    vel0: object = None         # forward: initial velocities, None when input_steps == 1; backward
+    pvs: object = None          # forward: rollout positions and velocities; backward
+    wprep: dict = None          # _unet_forward: split weight images {(conv, kind): pointer}; _encoder_forward
+    wprep_buf: object = None    # _unet_forward: the buffer behind wprep (kept alive)
+    logits: object = None       # _unet_forward (head not fused): the U-Net's logits; mask softmax, _unet_backward
+    head_in: object = None      # _unet_forward (head fused, else None): the head's input in unet_ws; mask softmax
+    unet_ws: object = None      # _unet_forward: the U-Net workspace; _unet_grad, _unet_backward; release drops it
+    unet_flags: int = 0         # _unet_forward: paig_unet_*_ex flags; _unet_grad, _unet_backward
+    unet_wp: tuple = None       # _unet_forward: (forward, dgrad) weight-image arrays; _unet_backward
+    dense_tail: bool = False    # _encoder_forward: l2 + head ran fused; _encoder_backward
+    w2t: object = None          # _encoder_forward: W2^T scratch when wprep has none (kept alive)
+    masks: object = None        # _encoder_forward; forward's result, _encoder_backward
+    objs: object = None         # _encoder_forward; forward's result
+    l1_x: object = None         # _encoder_forward: l1's input (the objects, pooled for the UNet); _encoder_backward
+    h1: object = None           # _encoder_forward: l1's output; _encoder_backward
+    h2: object = None           # _encoder_forward: l2's output; _encoder_backward
+    h3: object = None           # _encoder_forward: the position head's pre-activation; _encoder_backward
+    enc_pos: object = None      # _encoder_forward; forward's decoders and velocity encoder, backward
+    extra_slabs: list = field(default_factory=list)   # backward stages: (slab, rows, len, grad); _unet_backward
+    consumed: bool = False      # release; check_fresh
+    probe_cb: object = None     # Engine._unet_probe: the ctypes callback, alive as long as the state
+
+    def release(self):
+        """Drop the forward's U-Net workspace (activations, gradients, max-|x|
+        slots, pool codes) once its backward has been queued, or there is none;
+        stream order keeps the allocator's next user behind every kernel that
+        reads it.  The state then admits no second backward (retain_graph=True)."""
+        self.unet_ws = None
+        self.consumed = True
+
+    def check_fresh(self):
+        if self.consumed:
+            raise PaigError("a second backward through one forward (retain_graph=True) is not supported: the "
+                            "forward's saved state (its U-Net workspace) was released by the first backward")
+
+
 class Engine:
     """Binds a PhysicsNet's parameters to the HIP kernels."""
 
@@ -191,7 +314,6 @@ class Engine:
         self.probe = None
         self.last_masked_objs = None
         self.last_loss_handoff = None   # the last forward's loss-weight hand-off (physics_models._LossHandoff)
-        self._side = None   # second stream (see _fork)
         # called once per backward when the early gradient bucket is final
         # (FlatParams.allreduce_early by default; bench.py splits its HIP graph here)
         self.bucket_hook = model._flat.allreduce_early
@@ -279,12 +401,12 @@ class Engine:
                 self.L.paig_gemm_ex(0, 0, rows, I, O, 1.0, ptr(dy), O, ptr(W), I, 0.0, ptr(dx), I, None, 0, auxm,
                                     ptr(aux), I, None, ptr(ws), n_ws, self.gemm_math(self.DGRAD), st)
 
-    def dense_tail(self):
+    def dense_tail(self, sw):
         """The localiser's l2 + head as fp32 FMA inside the launches around
         them (paig_dense_tail_fwd / paig_head_l2_bwd): in split arithmetic,
         where the 3-MFMA l2 GEMMs were latency-bound launches of their own;
         bf16 keeps its 1-MFMA l2 GEMMs (faster there).  PAIG_DENSE_TAIL=0: A/B."""
-        return self.gemm_math(self.FWD) == 6 and os.environ.get("PAIG_DENSE_TAIL", "1") != "0"
+        return self.gemm_math(self.FWD) == 6 and sw.dense_tail
 
     def workspace_floats(self, lay):
         K, F, B = lay.K, lay.F, lay.B
@@ -298,148 +420,145 @@ class Engine:
                 self.L.paig_gemm_parts_size(K * F, 200, n1, self.gemm_math(self.FWD))]
         return int(max(need))
 
+    # -- argument packs (each built in one place, splatted at every call) ----
+    def _velmlp_params(self):
+        """The velocity MLP's (W0, b0, W2, b2, W4, b4) pointers."""
+        pm = "velocity_encoder.init_vel_mlp."
+        return tuple(ptr(self.p(pm + n)) for n in ("0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias"))
+
+    def _vfn_fwd_args(self, S):
+        """paig_vfn_fwd_multi's arrays: (n, W1, b1, W2, b2, hidden, raw, post-sigmoid, sizes)."""
+        return (3, *[_parr([ptr(self.p(nm + suf)) for nm in _VFN])
+                     for suf in (".l1.weight", ".l1.bias", ".l2.weight", ".l2.bias")],
+                *[_parr([ptr(S.src[nm][i]) for nm in _VFN]) for i in range(3)], _iarr(S.lay.vfn_sizes))
+
+    def _vfn_bwd_args(self, S, dsrc, vparts):
+        """paig_vfn_bwd*_multi's arrays: (n, d output, raw output, sigmoid?,
+        hidden, W2, dW1, db1, dW2, db2, block partials, sizes); dsrc = [d
+        template | d sigmoid(content) | d sigmoid(background)]."""
+        P = S.lay.vfn_sizes
+        return (3, _parr([ptr(dsrc) + o * 4 for o in (0, P[0], P[0] + P[1])]),
+                _parr([ptr(S.src[nm][1]) for nm in _VFN]), _iarr([0, 1, 1]),
+                _parr([ptr(S.src[nm][0]) for nm in _VFN]), _parr([ptr(self.p(nm + ".l2.weight")) for nm in _VFN]),
+                *[_parr([ptr(self.g(nm + suf)) for nm in _VFN])
+                  for suf in (".l1.weight", ".l1.bias", ".l2.weight", ".l2.bias")],
+                _parr([ptr(pt) for pt in vparts]), _iarr(P))
+
+    def _rollout_args(self, S):
+        """(cell, pos0, ld, vel0, dt, p0, p1, pvs, B, D, R): the rollout starts
+        at the last input step's encoded positions."""
+        lay = S.lay
+        dt, p0, p1 = self.cell_params(lay)
+        return (lay.cell, ptr(S.enc_pos) + (lay.ins - 1) * lay.D * 4, lay.Te * lay.D, ptr(S.vel0), ptr(dt), ptr(p0),
+                ptr(p1), ptr(S.pvs), lay.B, lay.D, lay.R)
+
+    def _head_bwd_prefix(self, S, denc, dh2, hslab):
+        """(h2, h3, d enc_pos, W3, d h2, slab, F, K, 200, H/2) of every paig_head*_bwd* entry point."""
+        lay = S.lay
+        return (ptr(S.h2), ptr(S.h3), ptr(denc), ptr(self.p("encoder.l3.weight")), ptr(dh2), ptr(hslab), lay.F, lay.K,
+                200, float(lay.H / 2))
+
     # -- forward ---------------------------------------------------------
+    def new_state(self, lay, x, need_saved):
+        """The saved state of one forward over x (contiguous fp32): the
+        layout's switches, the dense layers' workspace and the view of the
+        encoder's frames (frame n = b*Te + t of x's sequences, or x's own
+        frames for the standalone encoder / U-Net calls)."""
+        S = StepState()
+        S.lay, S.x, S.need_saved, S.sw = lay, x, need_saved, lay.sw
+        S.dev = x.device
+        S.cm = self.conv_flags()
+        S.ws = _empty(self.workspace_floats(lay), S.dev)
+        S.x_view = (ptr(x), lay.T * lay.frame, lay.Te, lay.frame) if lay.sequences else (ptr(x), lay.frame, 0, 0)
+        return S
+
     def forward(self, x, need_saved=True):
         require_device(x)
         model = self.model
         model._flat.ensure()
         B, T = x.shape[0], x.shape[1]
-        lay = Layout(model, B, T)
-        dev = x.device
-        st = stream_handle(dev)
+        lay = Layout(model, B, T, read_switches())
         L = self.L
         x = x.contiguous()
+        S = self.new_state(lay, x, need_saved)
+        dev, ws, sw = S.dev, S.ws, S.sw
+        st = stream_handle(dev)
         K, F, HW, H, h, D = lay.K, lay.F, lay.HW, lay.H, lay.h, lay.D
-        ws = _empty(self.workspace_floats(lay), dev)
-        S = {"lay": lay, "x": x, "ws": ws, "dev": dev, "need_saved": need_saved}
-        cm = self.conv_flags()
-        S["cm"] = cm
 
-        # ---- VariableFromNetwork sources (once per step, Q12): allocated here,
-        # computed on the main stream while the side stream runs the velocity
-        # MLP + rollout (only the decoders read them)
-        src = {}
-        vf = (("var_net_template", K * h * h, False), ("var_net_content", K * 3 * h * h, False),
-              ("var_net_background", 3 * HW, True))
-        for nm, P, post in vf:
-            src[nm] = (_empty(200, dev), _empty(P, dev), _empty(P, dev) if post else None)
-        S["src"] = src
-        tmpl, cont, bgp = src["var_net_template"][1], src["var_net_content"][1], src["var_net_background"][2]
+        # ---- VariableFromNetwork sources (once per step, Q12; only the decoders read them)
+        S.src = {nm: (_empty(200, dev), _empty(P, dev), _empty(P, dev) if nm == "var_net_background" else None)
+                 for nm, P in zip(_VFN, lay.vfn_sizes)}
+        tmpl, cont, bgp = S.src["var_net_template"][1], S.src["var_net_content"][1], S.src["var_net_background"][2]
 
         # ---- encoder over the first Te frames of every sequence (in place)
-        x_view = (ptr(x), T * lay.frame, lay.Te, lay.frame)   # frame n = b*Te + t
         # the rollout decoders' targets: x's frames, or (byte targets bound to
         # this input buffer) the dataset rows it was gathered from, as bytes.
         # The reconstruction targets are the encoder's frames, which the
         # gather writes as fp32 in either case: read there (no row lookup)
         bt = self.byte_targets
         if bt is not None and bt.covers(x, lay):
-            tb = 1
-            tgt_roll = (bt.base + lay.ins * lay.frame, bt.idx_ptr, T * lay.frame, lay.R, lay.frame)
+            S.tb = 1
+            S.tgt_roll = (bt.base + lay.ins * lay.frame, bt.idx_ptr, T * lay.frame, lay.R, lay.frame)
         else:
-            tb = 0
-            tgt_roll = (ptr(x) + lay.ins * lay.frame * 4, T * lay.frame, lay.R, lay.frame)
-        S.update(tb=tb, tgt_roll=tgt_roll)
-        self._encoder_forward(S, lay, x_view, ws, st)
-        masks, objs, enc_pos = S["masks"], S["objs"], S["enc_pos"]
+            S.tgt_roll = (ptr(x) + lay.ins * lay.frame * 4, T * lay.frame, lay.R, lay.frame)
+        self._encoder_forward(S, st)
+        enc_pos = S.enc_pos
 
         # Two independent chains follow the position head: velocity MLP ->
         # physics rollout (one thread per sequence: latency-bound, a few
         # blocks) and VFN sources -> reconstruction decode of all B*Te frames.
-        # They run on one stream (see _one_stream); PAIG_SCHED=0 puts the first
-        # on a side stream.  Everything a side chain touches is allocated
-        # before the fork.
+        # They share the step's one stream, merged into common launches where
+        # the shape allows.
         recons = _empty(F * lay.frame, dev)
         sse_rec = _empty(F, dev)
-        vel0 = None
-        vel_args = None
         if lay.ins > 1:
-            S_in = lay.ins
-            cols = 2 * (S_in - 1 if lay.alt_vel else S_in)
-            Xv = _empty(K * B * cols, dev)
-            vel0 = _empty(K * B * 2, dev)
-            if lay.alt_vel:
-                S.update(Xv=Xv)
+            S.Xv = _empty(K * B * 2 * (lay.ins - 1 if lay.alt_vel else lay.ins), dev)
+            S.vel0 = _empty(K * B * 2, dev)
+            if not lay.alt_vel:
+                S.v1 = _empty(K * B * 100, dev)
+                S.v2 = _empty(K * B * 100, dev)
+        S.pvs = _empty(B * (lay.R + 1) * 2 * D, dev)
+        roll = self._rollout_args(S)
+        vel_act = (ptr(S.Xv), ptr(S.v1), ptr(S.v2), ptr(S.vel0))
+        dec = (ptr(enc_pos), 0, 2 * K, 0, ptr(tmpl), ptr(cont), ptr(bgp), ptr(recons), lay.frame, *S.x_view,
+               ptr(sse_rec), F, K, h, H)
+        # velocity MLP + VFN sources in one launch (independent); then the
+        # rollout and the reconstruction decode in one launch
+        fuse_vfn = S.vel0 is not None and not lay.alt_vel and sw.fuse_vfn
+        merge_roll = fuse_vfn and self._merge_roll_rec(lay)
+        if fuse_vfn:
+            L.paig_velmlp_vfn_fwd(ptr(enc_pos), B, lay.Te, K, lay.ins, *self._velmlp_params(), *vel_act,
+                                  *self._vfn_fwd_args(S), st)
+        elif S.vel0 is not None and lay.alt_vel:
+            L.paig_vel_pack(ptr(enc_pos), ptr(S.Xv), B, lay.Te, K, lay.ins, 1, st)
+            self.linear(S.Xv, K * B, "velocity_encoder.init_vel_linear", S.vel0, 0, st, ws)
+        elif S.vel0 is not None:   # the whole MLP (packing fused) in one launch
+            L.paig_velmlp_fwd(ptr(enc_pos), B, lay.Te, K, lay.ins, *self._velmlp_params(), *vel_act, st)
+        if not merge_roll:   # the physics rollout (all R steps in one launch)
+            L.paig_rollout_fwd(*roll, st)
+        if not fuse_vfn:
+            L.paig_vfn_fwd_multi(*self._vfn_fwd_args(S), st)
+        # reconstruction decode (all B*Te frames, SSE vs input fused)
+        with self._p("dec_fwd:recon+rollout" if merge_roll else "dec_fwd:recon", 0, self._dec_bytes(F, lay)):
+            if merge_roll:
+                L.paig_decoder_fwd_rollout(*roll, *dec, st)
             else:
-                v1 = _empty(K * B * 100, dev)
-                v2 = _empty(K * B * 100, dev)
-                S.update(Xv=Xv, v1=v1, v2=v2)
-        S["vel0"] = vel0
-        pvs = _empty(B * (lay.R + 1) * 2 * D, dev)
-        prm = self.cell_params(lay)
-        S["pvs"] = pvs
-
-        def velocity(q):   # velocity encoder, then the physics rollout (all R steps in one launch)
-            if vel0 is not None:
-                if lay.alt_vel:
-                    L.paig_vel_pack(ptr(enc_pos), ptr(S["Xv"]), B, lay.Te, K, lay.ins, 1, q)
-                    self.linear(S["Xv"], K * B, "velocity_encoder.init_vel_linear", vel0, 0, q, ws)
-                else:   # the whole MLP (packing fused) in one launch
-                    pm = "velocity_encoder.init_vel_mlp."
-                    L.paig_velmlp_fwd(ptr(enc_pos), B, lay.Te, K, lay.ins, *[ptr(self.p(pm + n)) for n in (
-                        "0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias")], ptr(S["Xv"]),
-                        ptr(S["v1"]), ptr(S["v2"]), ptr(vel0), q)
-            L.paig_rollout_fwd(lay.cell, ptr(enc_pos) + (lay.ins - 1) * D * 4, lay.Te * D, ptr(vel0), ptr(prm[0]),
-                               ptr(prm[1]), ptr(prm[2]), ptr(pvs), B, D, lay.R, q)
-
-        def vfn_src(q):    # VariableFromNetwork sources
-            L.paig_vfn_fwd_multi(3, *[_parr([ptr(self.p(nm + suf)) for nm, _, _ in vf])
-                                      for suf in (".l1.weight", ".l1.bias", ".l2.weight", ".l2.bias")],
-                                 _parr([ptr(src[nm][0]) for nm, _, _ in vf]),
-                                 _parr([ptr(src[nm][1]) for nm, _, _ in vf]),
-                                 _parr([ptr(src[nm][2]) for nm, _, _ in vf]), _iarr([P for _, P, _ in vf]), q)
-
-        def dec_rec(q):    # reconstruction decode (all B*Te frames, SSE vs input fused)
-            with self._p("dec_fwd:recon", 0, self._dec_bytes(F, lay)):
-                L.paig_decoder_fwd(ptr(enc_pos), 0, 2 * K, 0, ptr(tmpl), ptr(cont), ptr(bgp), ptr(recons),
-                                   lay.frame, *x_view, ptr(sse_rec), F, K, h, H, q)
-
-        if self._one_stream():
-            if vel0 is not None and not lay.alt_vel and os.environ.get("PAIG_FUSE_VFN", "1") != "0":
-                # velocity MLP + VFN sources in one launch (independent), then the rollout
-                pm = "velocity_encoder.init_vel_mlp."
-                L.paig_velmlp_vfn_fwd(ptr(enc_pos), B, lay.Te, K, lay.ins, *[ptr(self.p(pm + n)) for n in (
-                    "0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias")], ptr(S["Xv"]), ptr(S["v1"]),
-                    ptr(S["v2"]), ptr(vel0), 3, *[_parr([ptr(self.p(nm + suf)) for nm, _, _ in vf])
-                                                  for suf in (".l1.weight", ".l1.bias", ".l2.weight", ".l2.bias")],
-                    _parr([ptr(src[nm][0]) for nm, _, _ in vf]), _parr([ptr(src[nm][1]) for nm, _, _ in vf]),
-                    _parr([ptr(src[nm][2]) for nm, _, _ in vf]), _iarr([P for _, P, _ in vf]), st)
-                if self._merge_roll_rec(lay):
-                    # the rollout and the reconstruction decode in one launch
-                    with self._p("dec_fwd:recon+rollout", 0, self._dec_bytes(F, lay)):
-                        L.paig_decoder_fwd_rollout(
-                            lay.cell, ptr(enc_pos) + (lay.ins - 1) * D * 4, lay.Te * D, ptr(vel0), ptr(prm[0]),
-                            ptr(prm[1]), ptr(prm[2]), ptr(pvs), B, D, lay.R, ptr(enc_pos), 0, 2 * K, 0, ptr(tmpl),
-                            ptr(cont), ptr(bgp), ptr(recons), lay.frame, *x_view, ptr(sse_rec), F, K, h, H, st)
-                else:
-                    L.paig_rollout_fwd(lay.cell, ptr(enc_pos) + (lay.ins - 1) * D * 4, lay.Te * D, ptr(vel0),
-                                       ptr(prm[0]), ptr(prm[1]), ptr(prm[2]), ptr(pvs), B, D, lay.R, st)
-                    dec_rec(st)
-            else:
-                velocity(st)
-                vfn_src(st)
-                dec_rec(st)
-        else:
-            sst = self._fork(dev)
-            velocity(sst)                  # (side) velocity encoder + rollout
-            vfn_src(st)                    # (main) VFN sources, reconstruction decode
-            dec_rec(st)
-            self._join(dev)
+                L.paig_decoder_fwd(*dec, st)
 
         # ---- rollout decode (all B*R frames in one launch, SSE vs input[:, ins:])
         out = _empty(B * lay.R * lay.frame, dev)
         sse_roll = _empty(B * lay.R, dev)
-        dec_fwd = L.paig_decoder_fwd_t8 if tb else L.paig_decoder_fwd
-        with self._p("dec_fwd:rollout", 0, self._dec_bytes(B * lay.R, lay, tb or 4)):
-            dec_fwd(ptr(pvs) + 2 * D * 4, (lay.R + 1) * 2 * D, 2 * D, lay.R, ptr(tmpl), ptr(cont), ptr(bgp),
-                    ptr(out), lay.frame, *tgt_roll, ptr(sse_roll), B * lay.R, K, h, H, st)
-        S["x_view"] = x_view
+        dec_fwd = L.paig_decoder_fwd_t8 if S.tb else L.paig_decoder_fwd
+        with self._p("dec_fwd:rollout", 0, self._dec_bytes(B * lay.R, lay, S.tb or 4)):
+            dec_fwd(ptr(S.pvs) + 2 * D * 4, (lay.R + 1) * 2 * D, 2 * D, lay.R, ptr(tmpl), ptr(cont), ptr(bgp),
+                    ptr(out), lay.frame, *S.tgt_roll, ptr(sse_roll), B * lay.R, K, h, H, st)
 
+        masks, objs = S.masks, S.objs
         res = {
             "output_seq": out.view(B, lay.R, 3, H, H),
             "recons_out": recons.view(B, lay.Te, 3, H, H),
             "enc_pos": enc_pos.view(B, lay.Te, D),
-            "pos_vel_seq": pvs.view(B, lay.R + 1, 2 * D),
+            "pos_vel_seq": S.pvs.view(B, lay.R + 1, 2 * D),
             "enc_masks": masks.view(F, K + 1, H, H),
             "masked_objs": [objs[k * F * 3 * HW:(k + 1) * F * 3 * HW].view(F, 3, H, H) for k in range(K)],
             "sse_rec": sse_rec,
@@ -449,7 +568,7 @@ class Engine:
             "background_content": bgp.view(1, 3, H, H),
         }
         if not need_saved:
-            self._release(S)
+            S.release()
         return res, (S if need_saved else None)
 
     # (K, H, cell) of paig_decoder_fwd_rollout (the one-CU decoder's shapes)
@@ -462,18 +581,9 @@ class Engine:
         blocks per CU (B=100: 500 + 1 blocks; B >= 512 measured 0.4-0.6%
         slower merged).  PAIG_MERGE_ROLL=0: two launches (the A/B)."""
         nt = self._ROLL_REC.get((lay.K, lay.H, lay.cell))
-        if nt is None or os.environ.get("PAIG_MERGE_ROLL", "1") == "0":
+        if nt is None or not lay.sw.merge_roll:
             return False
         return min((lay.F + 1) // 2, 1024) + -(-lay.B // nt) <= 1024
-
-    def _release(self, S):
-        """Drop a forward's U-Net workspace (activations, gradients, max-|x|
-        slots, pool codes) once its backward has been queued, or there is
-        none; stream order keeps the allocator's next user behind every kernel
-        that reads it.  The saved state then admits no second backward
-        (retain_graph=True)."""
-        S.pop("unet_ws", None)
-        S["consumed"] = True
 
     # probe kinds of paig_unet_*_ex (include/paig_hip.h PAIG_PROBE_*) -> tag prefix
     _PROBE_TAG = {0: "conv_fwd", 1: "conv_bwd", 2: "conv_wgrad", 3: "conv_dgrad"}
@@ -486,7 +596,7 @@ class Engine:
         FLOPs and HBM bytes (bench.py's roofline); None when not probing."""
         if self.probe is None:
             return None
-        lay, F = S["lay"], S["lay"].F
+        lay, F = S.lay, S.lay.F
         open_ = {}
 
         def cb(ctx, ev, op, conv, kind, cin, cout, Hl, fl):
@@ -515,24 +625,22 @@ class Engine:
             c.__enter__()
             open_[op] = c
 
-        f = self._PROBE_FN(cb)
-        S["_probe_cb"] = f   # alive as long as the saved state
-        return ctypes.cast(f, ctypes.c_void_p)
+        S.probe_cb = self._PROBE_FN(cb)   # alive as long as the saved state
+        return ctypes.cast(S.probe_cb, ctypes.c_void_p)
 
-    def _unet_forward(self, S, lay, x_view, st, fuse_head=False):
-        """The U-Net over F frames addressed by x_view (frame view pointer,
-        stride, group, group stride): the C interpreter of csrc/unet.hip
-        (paig_unet_fwd_ex) in one workspace that the backward reuses; S["acts"]
-        holds the logits ("LG"), or, fuse_head, the 1x1 head's input ("head":
-        c12's / c17's output, which the encoder's fused mask softmax reads)."""
+    def _unet_forward(self, S, st, fuse_head=False):
+        """The U-Net over the F frames of S.x_view: the C interpreter of
+        csrc/unet.hip (paig_unet_fwd_ex) in one workspace that the backward
+        reuses.  Leaves the logits (S.logits), or, fuse_head, the 1x1 head's
+        input (S.head_in: c12's / c17's output, which the encoder's fused mask
+        softmax reads)."""
         L = self.L
+        lay, sw, dev, cm = S.lay, S.sw, S.dev, S.cm
         F, H, K = lay.F, lay.H, lay.K
-        dev = S["dev"]
-        cm = S["cm"]
-        flags = ((1 if fuse_head else 0) | (0 if S.get("need_saved", True) else 4) |
-                 (2 if os.environ.get("PAIG_FUSED_BWD", "1") == "0" else 0) |
-                 (16 if os.environ.get("PAIG_UPT", "1") == "0" else 0) |   # A/B: standalone upsample backward
-                 (32 if os.environ.get("PAIG_POOL_FOLD", "1") == "0" else 0))   # A/B: standalone pool backward
+        flags = ((1 if fuse_head else 0) | (0 if S.need_saved else 4) |
+                 (0 if sw.fused_bwd else 2) |   # A/B: separate data / weight gradient launches
+                 (0 if sw.upt else 16) |        # A/B: standalone upsample backward
+                 (0 if sw.pool_fold else 32))   # A/B: standalone pool backward
         Ws = [self.p(lay.prefix + f"c{c + 1}.weight") for c in range(lay.nconv)]
         Bs = [self.p(lay.prefix + f"c{c + 1}.bias") for c in range(lay.nconv)]
         # split path: every conv's forward and dgrad weight images (and the
@@ -549,7 +657,7 @@ class Engine:
                 if c > 0:   # the dgrad kernel's images (Q10: none for the input layer)
                     jobs.append((c, 1, W_, cout, cin, ks))
             sizes = [int(L.paig_conv_wprep_size(j[3], j[4], j[5])) for j in jobs]
-            if self.dense_tail():
+            if self.dense_tail(sw):
                 jobs.append((-1, 2, self.p("encoder.l2.weight"), 200, 200, 1))
                 sizes.append(2 * 200 * 200)
             buf = torch.empty(sum(-(-n // 8) * 8 for n in sizes), dtype=torch.int16, device=dev)
@@ -561,63 +669,58 @@ class Engine:
             n = len(jobs)
             # deferred: the U-Net's first conv carries the prep in its own
             # launch (PAIG_WPREP_MERGE=0: a separate launch, the A/B)
-            wprep = L.paig_conv_wprep_defer if os.environ.get("PAIG_WPREP_MERGE", "1") != "0" else L.paig_conv_wprep
+            wprep = L.paig_conv_wprep_defer if sw.wprep_merge else L.paig_conv_wprep
             wprep(n, (ctypes.c_void_p * n)(*[ptr(j[2]) for j in jobs]),
                   (ctypes.c_int * n)(*[j[3] for j in jobs]), (ctypes.c_int * n)(*[j[4] for j in jobs]),
                   (ctypes.c_int * n)(*[j[5] for j in jobs]), (ctypes.c_int * n)(*[j[1] for j in jobs]),
                   (ctypes.c_void_p * n)(*outs), st)
-            S["wprep_buf"] = buf
+            S.wprep_buf = buf
             wpf = _parr([wp[(c, 0)] for c in range(lay.nconv)])
             wpd = _parr([wp.get((c, 1), 0) for c in range(lay.nconv)])
-        S["wprep"] = wp
+        S.wprep = wp
         nb = int(L.paig_unet_workspace_ex(lay.net, F, H, K, cm, flags))
         if nb <= 0:
             raise PaigError(f"paig_unet_workspace_ex: no U-Net for net={lay.net} F={F} H={H} K={K} math={cm}")
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)
         logits = None if fuse_head else _empty(F * K * lay.HW, dev)
         probe = self._unet_probe(S)
-        L.paig_unet_fwd_ex(lay.net, F, H, K, cm, flags, *x_view, _parr([ptr(t) for t in Ws]),
+        L.paig_unet_fwd_ex(lay.net, F, H, K, cm, flags, *S.x_view, _parr([ptr(t) for t in Ws]),
                            _parr([ptr(t) for t in Bs]), ptr(logits), wpf, wpd, ptr(ws), nb, probe, None, st)
-        acts = {}
         if fuse_head:
             off = int(L.paig_unet_buffer(lay.net, F, H, K, cm, flags, 0, lay.head_buf))
-            acts["head"] = ws[off:off + F * lay.head_ci * lay.HW * 4].view(torch.float32)
-        else:
-            acts["LG"] = logits
-        S.update(acts=acts, head_fused=fuse_head, unet_ws=ws, unet_flags=flags, unet_wp=(wpf, wpd))
+            S.head_in = ws[off:off + F * lay.head_ci * lay.HW * 4].view(torch.float32)
+        S.logits, S.unet_ws, S.unet_flags, S.unet_wp = logits, ws, flags, (wpf, wpd)
 
     def _unet_grad(self, S, buf, n):
         """The U-Net workspace's gradient buffer `buf` (n floats)."""
-        lay = S["lay"]
-        off = int(self.L.paig_unet_buffer(lay.net, lay.F, lay.H, lay.K, S["cm"], S["unet_flags"], 1, buf))
+        lay = S.lay
+        off = int(self.L.paig_unet_buffer(lay.net, lay.F, lay.H, lay.K, S.cm, S.unet_flags, 1, buf))
         assert off >= 0, f"no gradient buffer {buf} in the U-Net workspace"
-        return S["unet_ws"][off:off + n * 4].view(torch.float32)
+        return S.unet_ws[off:off + n * 4].view(torch.float32)
 
-    def _encoder_forward(self, S, lay, x_view, ws, st):
+    def _encoder_forward(self, S, st):
         """ConvolutionalEncoder.forward (nn/network/blocks.py:77-103) over the
-        frames of x_view: U-Net, mask softmax x image, l1/l2, position head."""
+        frames of S.x_view: U-Net, mask softmax x image, l1/l2, position head."""
         L = self.L
+        lay, x_view, ws, dev = S.lay, S.x_view, S.ws, S.dev
         F, H, HW, K = lay.F, lay.H, lay.HW, lay.K
-        dev = S["dev"]
-        S["x_view"] = x_view
-        self._unet_forward(S, lay, x_view, st, fuse_head=lay.fuse_head)
-        acts = S["acts"]
+        self._unet_forward(S, st, fuse_head=lay.fuse_head)
         # ---- mask softmax + masked objects + localiser MLP + position head
         masks = _empty(F * (K + 1) * HW, dev)
         objs = _empty(K * F * 3 * HW, dev)
         pobjs = _empty(K * F * lay.l1_in, dev) if lay.unet else None
         if lay.fuse_head:   # the head conv + cat(ones) + softmax + mask x image (+ AvgPool2d), one launch
             hn = lay.prefix + lay.head_name
-            L.paig_head_mask_fwd_ex(ptr(acts["head"]), ptr(self.p(hn + ".weight")), ptr(self.p(hn + ".bias")),
+            L.paig_head_mask_fwd_ex(ptr(S.head_in), ptr(self.p(hn + ".weight")), ptr(self.p(hn + ".bias")),
                                     *x_view, ptr(masks), ptr(objs), ptr(pobjs), F, K, lay.head_ci, H, H,
                                     lay.head_flags, st)
         else:
-            L.paig_mask_softmax_fwd(ptr(acts["LG"]), *x_view, ptr(masks), ptr(objs), ptr(pobjs), F, K, 3, H, H, st)
+            L.paig_mask_softmax_fwd(ptr(S.logits), *x_view, ptr(masks), ptr(objs), ptr(pobjs), F, K, 3, H, H, st)
         l1_x = pobjs if lay.unet else objs
         h1 = _empty(K * F * 200, dev)
         h2 = _empty(K * F * 200, dev)
         h3 = _empty(K * F * 2, dev)
-        if not self.dense_tail():
+        if not self.dense_tail(S.sw):
             self.linear(l1_x, K * F, "encoder.l1", h1, 1, st, ws)
             self.linear(h1, K * F, "encoder.l2", h2, 1, st, ws)
             enc_pos = _empty(F * 2 * K, dev)
@@ -626,7 +729,7 @@ class Engine:
         else:
             # l1 (blocks.py:98) as split-K slabs, then ONE launch for its
             # epilogue, l2 and the position head (blocks.py:99-102)
-            S["dense_tail"] = True
+            S.dense_tail = True
             n1, KF = lay.l1_in, K * F
             enc_pos = _empty(F * 2 * K, dev)
             with self._p("gemm_fwd:encoder.l1", 2 * KF * 200 * n1, 4 * (KF * n1 + 200 * n1)):
@@ -636,42 +739,16 @@ class Engine:
                 raise PaigError(f"paig_gemm_parts failed (rc={nS}): {L.paig_last_error().decode(errors='replace')}")
             with self._p("dense_tail_fwd", 2 * KF * 200 * 200 + 4 * KF * 200,
                          4 * (nS * KF * 200 + 2 * KF * 200 + 200 * 200 + 2 * KF + 2 * KF)):
-                w2t = S.get("wprep", {}).get((-1, 2))   # W2^T from the step's weight-prep launch
+                w2t = S.wprep.get((-1, 2))   # W2^T from the step's weight-prep launch
                 w2 = None if w2t is not None else self.p("encoder.l2.weight")
                 if w2t is None:
-                    S["w2t"] = _empty(200 * 200, dev)
-                    w2t = ptr(S["w2t"])
+                    S.w2t = _empty(200 * 200, dev)
+                    w2t = ptr(S.w2t)
                 L.paig_dense_tail_fwd(ptr(ws), nS, ptr(self.p("encoder.l1.bias")), ptr(h1), ptr(w2), w2t,
                                       ptr(self.p("encoder.l2.bias")), ptr(h2),
                                       ptr(self.p("encoder.l3.weight")), ptr(self.p("encoder.l3.bias")), ptr(h3),
                                       ptr(enc_pos), F, K, 200, float(H / 2), st)
-        S.update(masks=masks, objs=objs, l1_x=l1_x, h1=h1, h2=h2, h3=h3, enc_pos=enc_pos)
-
-    # -- a second stream for the per-sequence chains (PAIG_SCHED=0 only) ----
-    def _fork(self, dev):
-        """Side stream ordered after everything issued so far on the current
-        stream; graph capture records the fork as a branch."""
-        if self._side is None or self._side.device != dev:
-            self._side = torch.cuda.Stream(dev)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
-        self._side.wait_event(ev)
-        return self._side.cuda_stream
-
-    def _one_stream(self):
-        """The per-sequence chains (velocity encoder, rollout and their
-        backward) and the decoder / VFN work run on ONE stream: inside a
-        replayed HIP graph every cross-stream edge costs 5-10 us of idle
-        queue even when it is long satisfied (tools/timeline.py), more than
-        the concurrent kernels overlapped (they slow each other down), so the
-        serial order measured 0.6% faster than the round-2 two-stream order
-        (PAIG_SCHED=0).  Probed runs keep one stream too."""
-        return os.environ.get("PAIG_SCHED", "2") != "0"
-
-    def _join(self, dev):
-        ev = torch.cuda.Event()
-        ev.record(self._side)
-        torch.cuda.current_stream(dev).wait_event(ev)
+        S.masks, S.objs, S.l1_x, S.h1, S.h2, S.h3, S.enc_pos = masks, objs, l1_x, h1, h2, h3, enc_pos
 
     def cell_params(self, lay):
         m = self.model
@@ -683,65 +760,52 @@ class Engine:
         return dt, None, None
 
     # -- backward --------------------------------------------------------
+    def _decoder_bwd(self, S, pos, po, pi, pg, tgt, dsse, lw, dout, dpos, slab_p, scr, nfr, live, st):
+        """paig_decoder_bwd_ex over nfr frames at positions (pos, po, pi, pg):
+        fp32 (4-tuple) or byte (5-tuple) targets tgt; lw: in-kernel loss
+        weights (mode, LossAdjoints) or None (dsse read)."""
+        lay = S.lay
+        tf, t8, ti = (tgt[0], None, None) if len(tgt) == 4 else (None, tgt[0], tgt[1])
+        fs, grp, gs = tgt[-3:]
+        if lw is not None:
+            mode, adj = lw
+            lwa = (mode, ptr(adj.dt), ptr(adj.de), ptr(adj.dr), float(adj.ae), adj.B, adj.Te, adj.R, adj.pred)
+            dsse = None
+        else:
+            lwa = (0, None, None, None, 0.0, 0, 0, 0, 0)
+        self.L.paig_decoder_bwd_ex(pos, po, pi, pg, ptr(S.src["var_net_template"][1]), ptr(S.src["var_net_content"][1]),
+                                   ptr(S.src["var_net_background"][2]), tf, t8, ti, fs, grp, gs, ptr(dsse), *lwa,
+                                   ptr(dout), lay.frame, dpos, slab_p, scr, nfr, live, lay.K, lay.h, lay.H, st)
+
     def backward(self, S, d_sse_rec=None, d_sse_roll=None, d_out=None, d_recons=None, d_enc_pos=None, d_pvs=None,
                  roll_live=0, lossw=None):
         """Writes every live parameter gradient into the model's flat grad buffer.
         roll_live > 0: only the first roll_live rollout steps of every
         sequence have a loss weight (the others' d_sse_roll entries are zero
         and there is no dense d_out): the rollout decoder backward reads only
-        those frames.  lossw: {"rec" / "roll": (mode, (dt, de, dr, ae, B, Te,
-        R, pred))} -- that decoder forms its per-frame weights in-kernel from
-        the loss adjoints (paig_decoder_bwd_ex) instead of reading d_sse_*."""
-        self._check_fresh(S)
-        lay = S["lay"]
-        L = self.L
-        x = S["x"]
-        dev = x.device
+        those frames.  lossw: {"rec" / "roll": (mode, LossAdjoints)} -- that
+        decoder forms its per-frame weights in-kernel from the loss adjoints
+        (paig_decoder_bwd_ex) instead of reading d_sse_*."""
+        S.check_fresh()
+        lay, sw, dev, L = S.lay, S.sw, S.dev, self.L
         st = stream_handle(dev)
-        ws = S["ws"]
-        S["extra_slabs"] = []   # partial-gradient slabs reduced with the U-Net's at the end
-        K, F, HW, H, h, D, B, R = lay.K, lay.F, lay.HW, lay.H, lay.h, lay.D, lay.B, lay.R
-        tmpl = S["src"]["var_net_template"][1]
-        cont = S["src"]["var_net_content"][1]
-        bgp = S["src"]["var_net_background"][2]
-        tb = S["tb"]
-        lossw = lossw or {}
+        K, F, H, h, D, B, R = lay.K, lay.F, lay.H, lay.h, lay.D, lay.B, lay.R
+        lossw = dict(lossw or {})
 
-        if lossw and (K, H) not in ((2, 32), (3, 36), (2, 64)):
+        if (K, H) not in ((2, 32), (3, 36), (2, 64)):
             # in-kernel weights need the one-CU decoders: materialise them here
-            for key in list(lossw):
-                mode, (dt, de, dr, ae, lB, lTe, lR, lpred) = lossw.pop(key)
-                w = _empty(lB * (lTe if mode == 1 else lR), dev)
-                L.paig_loss_bwd(ptr(dt), ptr(de), ptr(dr), float(ae), ptr(w) if mode == 1 else None,
-                                ptr(w) if mode == 2 else None, lB, lTe, lR, lpred, st)
-                if mode == 1:
-                    d_sse_rec = w
-                else:
-                    d_sse_roll = w
-
-        def dec_bwd(q, pos, po, pi, pg, tgt, dsse, lw, dout, dpos, slab_p, scr, nfr, live):
-            """paig_decoder_bwd_ex: fp32 (4-tuple) or byte (5-tuple) targets; lw:
-            in-kernel loss weights or None (dsse read)"""
-            tf, t8, ti = (tgt[0], None, None) if len(tgt) == 4 else (None, tgt[0], tgt[1])
-            fs, grp, gs = tgt[-3:]
-            if lw is not None:
-                mode, (dt, de, dr, ae, lB, lTe, lR, lpred) = lw
-                lwa = (mode, ptr(dt), ptr(de), ptr(dr), float(ae), lB, lTe, lR, lpred)
-                dsse = None
-            else:
-                lwa = (0, None, None, None, 0.0, 0, 0, 0, 0)
-            L.paig_decoder_bwd_ex(pos, po, pi, pg, ptr(tmpl), ptr(cont), ptr(bgp), tf, t8, ti, fs, grp, gs, ptr(dsse),
-                                  *lwa, ptr(dout), lay.frame, dpos, slab_p, scr, nfr, live, K, h, H, q)
+            if "rec" in lossw:
+                d_sse_rec = materialise(lossw.pop("rec")[1], 1, dev)
+            if "roll" in lossw:
+                d_sse_roll = materialise(lossw.pop("roll")[1], 2, dev)
         if d_out is not None:
             d_out = d_out.contiguous()
         if d_recons is not None:
             d_recons = d_recons.contiguous()
 
-        # ---- buffers of the whole decoder / rollout / velocity backward (all
-        # allocated on the main stream before the fork below)
+        # ---- buffers of the whole decoder / rollout / velocity backward
         slab_len = int(L.paig_decoder_slab_len(K, h, H))
         roll_live = roll_live if (d_out is None and 0 < roll_live < R) else 0
-        S["roll_live"] = roll_live
         nb_rec = L.paig_decoder_bwd_blocks(F, 0, 0, K, h, H)
         nb_roll = L.paig_decoder_bwd_blocks(B * R, R, roll_live, K, h, H)
         slab = _empty((nb_rec + nb_roll) * slab_len, dev)
@@ -750,159 +814,112 @@ class Engine:
         denc = _empty(F * D, dev)   # d enc_pos [B][Te][D]
         dpos_roll = _empty(B * R * D, dev)
         dsrc = _empty(slab_len, dev)
-        pvs = S["pvs"]
         dpos0 = _empty(B * D, dev)
-        dvel0 = _empty(K * B * 2, dev) if S["vel0"] is not None else None
+        dvel0 = _empty(K * B * 2, dev) if S.vel0 is not None else None
         rpart = _empty(2 * L.paig_rollout_bwd_blocks(B), dev, torch.float64)
         dXv = vslab = None
-        if S["vel0"] is not None:
+        if S.vel0 is not None:
             dXv = _empty(K * B * 2 * (lay.ins - 1 if lay.alt_vel else lay.ins), dev)
             if not lay.alt_vel:
                 vblk, vlen = L.paig_velmlp_bwd_blocks(K * B), L.paig_velmlp_slab_len(lay.ins)
                 vslab = _empty(vblk * vlen, dev)
-        vfn = (("var_net_template", K * h * h, 0, tmpl), ("var_net_content", K * 3 * h * h, 1, cont),
-               ("var_net_background", 3 * HW, 1, S["src"]["var_net_background"][1]))
-        vparts = [_empty(L.paig_vfn_bwd_blocks(P) * 200, dev) for _, P, _, _ in vfn]
+        vparts = [_empty(L.paig_vfn_bwd_blocks(P) * 200, dev) for P in lay.vfn_sizes]
+        if d_pvs is not None:
+            d_pvs = d_pvs.contiguous()
+        if d_enc_pos is not None:
+            d_enc_pos = d_enc_pos.contiguous()
 
+        # ---- rollout-frame decoder backward: d rollout positions + partial source grads
+        live_frames = B * roll_live if roll_live else B * R
+        with self._p("dec_bwd:rollout", 0, self._dec_bwd_bytes(live_frames, B * R, lay, d_out is not None, S.tb or 4)):
+            self._decoder_bwd(S, ptr(S.pvs) + 2 * D * 4, (R + 1) * 2 * D, 2 * D, R, S.tgt_roll, d_sse_roll,
+                              lossw.get("roll"), d_out, ptr(dpos_roll), ptr(slab) + nb_rec * slab_len * 4,
+                              ptr(scratch), B * R, roll_live, st)
+
+        # ---- rollout adjoint -> d pos0, d vel0, physics params; velocity encoder backward
         prm = self.cell_params(lay)
         gk = gq = None
         if lay.cell == 0:
             gk, gq = self.g("rollout_cell.k"), self.g("rollout_cell.equil")
         elif lay.cell == 2:
             gk = self.g("rollout_cell.g")
-        # the chains' inputs exist before any fork (a temporary made after it
-        # could be recycled by a main-stream allocation while a side kernel
-        # still reads it)
-        d_pvs_c = d_pvs.contiguous() if d_pvs is not None else None
-        d_enc_c = d_enc_pos.contiguous() if d_enc_pos is not None else None
-        live_frames = B * roll_live if roll_live else B * R
+        L.paig_rollout_bwd(lay.cell, ptr(S.pvs), ptr(dpos_roll), ptr(d_pvs), ptr(prm[0]), ptr(prm[1]), ptr(prm[2]),
+                           ptr(dpos0), ptr(dvel0), ptr(rpart), ptr(gk), ptr(gq), 0, B, D, R, st)
+        if S.vel0 is not None and lay.alt_vel:
+            self.linear_bwd(S.Xv, dvel0, K * B, "velocity_encoder.init_vel_linear", dXv, None, 0, st, S.ws)
+        elif S.vel0 is not None:   # one launch; its partial weight grads join the U-Net's batched slab reduction
+            W0, _, W2, _, W4, _ = self._velmlp_params()
+            L.paig_velmlp_bwd(ptr(dvel0), ptr(S.Xv), ptr(S.v1), ptr(S.v2), W0, W2, W4, ptr(dXv), ptr(vslab), K * B,
+                              lay.ins, st)
+            pm = "velocity_encoder.init_vel_mlp."
+            g0 = self.g(pm + "0.weight")
+            assert self.g(pm + "4.bias").data_ptr() == g0.data_ptr() + (vlen - 2) * 4, \
+                "velocity MLP grads not contiguous"
+            S.extra_slabs.append((vslab, vblk, vlen, g0))
 
-        def dec_roll(q):   # rollout-frame decoder backward: d rollout positions + partial source grads
-            with self._p("dec_bwd:rollout", 0, self._dec_bwd_bytes(live_frames, B * R, lay, d_out is not None, tb or 4)):
-                dec_bwd(q, ptr(pvs) + 2 * D * 4, (R + 1) * 2 * D, 2 * D, R, S["tgt_roll"], d_sse_roll,
-                        lossw.get("roll"), d_out, ptr(dpos_roll), ptr(slab) + nb_rec * slab_len * 4, ptr(scratch),
-                        B * R, roll_live)
+        # ---- reconstruction decoder backward: d enc_pos + partial source grads
+        with self._p("dec_bwd:recon", 0, self._dec_bwd_bytes(F, F, lay, d_recons is not None)):
+            self._decoder_bwd(S, ptr(S.enc_pos), 0, 2 * K, 0, S.x_view, d_sse_rec, lossw.get("rec"), d_recons,
+                              ptr(denc), ptr(slab), ptr(scratch), F, 0, st)
 
-        def dec_rec(q):    # reconstruction decoder backward: d enc_pos + partial source grads
-            with self._p("dec_bwd:recon", 0, self._dec_bwd_bytes(F, F, lay, d_recons is not None)):
-                dec_bwd(q, ptr(S["enc_pos"]), 0, 2 * K, 0, S["x_view"], d_sse_rec, lossw.get("rec"), d_recons,
-                        ptr(denc), ptr(slab), ptr(scratch), F, 0)
-
-        def physics(q):    # rollout adjoint -> d pos0, d vel0, physics params; velocity encoder backward
-            L.paig_rollout_bwd(lay.cell, ptr(pvs), ptr(dpos_roll), ptr(d_pvs_c), ptr(prm[0]), ptr(prm[1]),
-                               ptr(prm[2]), ptr(dpos0), ptr(dvel0), ptr(rpart), ptr(gk), ptr(gq), 0, B, D, R, q)
-            if S["vel0"] is not None:
-                if lay.alt_vel:
-                    self.linear_bwd(S["Xv"], dvel0, K * B, "velocity_encoder.init_vel_linear", dXv, None, 0, q, ws)
-                else:   # one launch; its partial weight grads join the U-Net's batched slab reduction
-                    pm = "velocity_encoder.init_vel_mlp."
-                    L.paig_velmlp_bwd(ptr(dvel0), ptr(S["Xv"]), ptr(S["v1"]), ptr(S["v2"]),
-                                      ptr(self.p(pm + "0.weight")), ptr(self.p(pm + "2.weight")),
-                                      ptr(self.p(pm + "4.weight")), ptr(dXv), ptr(vslab), K * B, lay.ins, q)
-                    g0 = self.g(pm + "0.weight")
-                    assert self.g(pm + "4.bias").data_ptr() == g0.data_ptr() + (vlen - 2) * 4, \
-                        "velocity MLP grads not contiguous"
-                    S["extra_slabs"].append((vslab, vblk, vlen, g0))
-
-        def sources(q, split=False):   # source-gradient reduction (both decoders' slab rows), VFN backward
-            L.paig_slab_reduce_multi(1, (ctypes.c_void_p * 1)(ptr(slab)), (ctypes.c_int * 1)(nb_rec + nb_roll),
-                                     (ctypes.c_int * 1)(slab_len), (ctypes.c_void_p * 1)(ptr(dsrc)), 0, q)
-            offs = [0, vfn[0][1], vfn[0][1] + vfn[1][1]]
-            args = (3, _parr([ptr(dsrc) + o * 4 for o in offs]), _parr([ptr(r) for _, _, _, r in vfn]),
-                    _iarr([sg for _, _, sg, _ in vfn]),
-                    _parr([ptr(S["src"][nm][0]) for nm, _, _, _ in vfn]),
-                    _parr([ptr(self.p(nm + ".l2.weight")) for nm, _, _, _ in vfn]),
-                    *[_parr([ptr(self.g(nm + suf)) for nm, _, _, _ in vfn])
-                      for suf in (".l1.weight", ".l1.bias", ".l2.weight", ".l2.bias")],
-                    _parr([ptr(pt) for pt in vparts]), _iarr([P for _, P, _, _ in vfn]))
-            if split:      # phase 1 here, phase 2 inside the head backward's launch
-                L.paig_vfn_bwd1_multi(*args, q)
-                return args
-            L.paig_vfn_bwd_multi(*args, q)
-            return None
-
-        if self._one_stream():
-            dec_roll(st)
-            physics(st)
-            dec_rec(st)
-            fuse_vel = os.environ.get("PAIG_FUSE_VEL", "1") != "0"
-            # VFN backward phase 2 inside the head backward's launch
-            vfn2 = sources(st, split=fuse_vel and os.environ.get("PAIG_FUSE_VFN2", "1") != "0")
-            if d_enc_c is not None:
-                L.paig_axpby(ptr(d_enc_c), ptr(denc), F * D, 1.0, 1.0, st)
-            # the velocity encoder's input gradient is added inside the head
-            # backward (PAIG_FUSE_VEL=0: the separate unpack-add launch)
-            vel = (dXv, dpos0, B, lay.Te, lay.ins, int(lay.alt_vel), vfn2)
-            if not fuse_vel:
-                L.paig_vel_unpack_add(ptr(dXv), ptr(dpos0), ptr(denc), B, lay.Te, K, lay.ins, int(lay.alt_vel), st)
-                vel = None
+        # ---- source-gradient reduction (both decoders' slab rows), then the VFN
+        # backward: whole, or phase 1 here and phase 2 inside the head backward's launch
+        L.paig_slab_reduce_multi(1, (ctypes.c_void_p * 1)(ptr(slab)), (ctypes.c_int * 1)(nb_rec + nb_roll),
+                                 (ctypes.c_int * 1)(slab_len), (ctypes.c_void_p * 1)(ptr(dsrc)), 0, st)
+        vfn2 = self._vfn_bwd_args(S, dsrc, vparts)
+        if sw.fuse_vel and sw.fuse_vfn2:
+            L.paig_vfn_bwd1_multi(*vfn2, st)
         else:
-            dec_roll(st)
-            sst = self._fork(dev)
-            physics(sst)   # (side) rollout adjoint + velocity encoder backward
-            dec_rec(st)    # (main) reconstruction decoder backward, source reduction, VFN backward
-            sources(st)
-            if d_enc_c is not None:
-                L.paig_axpby(ptr(d_enc_c), ptr(denc), F * D, 1.0, 1.0, st)
-            self._join(dev)
-            L.paig_vel_unpack_add(ptr(dXv), ptr(dpos0), ptr(denc), B, lay.Te, K, lay.ins, int(lay.alt_vel), st)
+            L.paig_vfn_bwd_multi(*vfn2, st)
+            vfn2 = None
+        if d_enc_pos is not None:
+            L.paig_axpby(ptr(d_enc_pos), ptr(denc), F * D, 1.0, 1.0, st)
+        # the velocity encoder's input gradient (dXv, dpos0, B, Te, ins, alt) is
+        # added inside the head backward (PAIG_FUSE_VEL=0: the separate
+        # unpack-add launch)
+        vel = (ptr(dXv), ptr(dpos0), B, lay.Te, lay.ins, int(lay.alt_vel))
+        if not sw.fuse_vel:
+            L.paig_vel_unpack_add(vel[0], vel[1], ptr(denc), B, lay.Te, K, lay.ins, int(lay.alt_vel), st)
             vel = None
-        del d_pvs_c, d_enc_c   # (kept alive across the side chain)
+        self._encoder_backward(S, denc, st, vel=vel, vfn2=vfn2)
 
-        self._encoder_backward(S, denc, st, vel=vel)
-
-    def _encoder_backward(self, S, denc, st, hook=True, vel=None):
+    def _encoder_backward(self, S, denc, st, hook=True, vel=None, vfn2=None):
         """ConvolutionalEncoder backward from d enc_pos (denc [F][2K]): position
-        head, l2/l1, mask softmax, U-Net; all its weight gradients."""
-        lay = S["lay"]
-        L = self.L
-        dev = S["dev"]
-        ws = S["ws"]
+        head, l2/l1, mask softmax, U-Net; all its weight gradients.  vel: the
+        velocity term (dXv, dpos0, B, Te, ins, alt) the head backward adds to
+        denc first, or None; vfn2: the VFN backward's phase 2 arguments
+        (_vfn_bwd_args) riding in the same launch, or None."""
+        lay, dev, ws, x_view, L = S.lay, S.dev, S.ws, S.x_view, self.L
         K, F, HW, H = lay.K, lay.F, lay.HW, lay.H
-        x_view = S["x_view"]
-        S.setdefault("extra_slabs", [])
         # ---- position head + localiser MLP backward -> d masked objects
         dh2 = _empty(K * F * 200, dev)
         dh1 = _empty(K * F * 200, dev)
-        fused_l2 = S.get("dense_tail", False)   # l2's data gradient formed inside the head backward's launch
+        fused_l2 = S.dense_tail   # l2's data gradient formed inside the head backward's launch
         hblk = L.paig_head_l2_bwd_blocks(K * F) if fused_l2 else L.paig_head_bwd_blocks(K * F)
         hslab = _empty(hblk * (2 * 200 + 2), dev)
+        head = self._head_bwd_prefix(S, denc, dh2, hslab)
         if fused_l2:
-            dXv = dpos0 = None
-            Bv = Tev = Sv = altv = 0
-            vfn2 = None
-            if vel is not None:
-                dXv, dpos0, Bv, Tev, Sv, altv, vfn2 = vel
-            vf = vfn2 if vfn2 is not None else (0,) + (None,) * 11
-            L.paig_head_l2_bwd(ptr(S["h2"]), ptr(S["h3"]), ptr(denc), ptr(self.p("encoder.l3.weight")), ptr(dh2),
-                               ptr(hslab), F, K, 200, float(H / 2), ptr(dXv) if torch.is_tensor(dXv) else dXv,
-                               ptr(dpos0) if torch.is_tensor(dpos0) else dpos0, Bv, Tev, Sv, altv,
-                               ptr(self.p("encoder.l2.weight")), ptr(S["h1"]), ptr(dh1), *vf, st)
-        elif vel is not None and vel[6] is not None:   # + the VFN backward's phase 2
-            dXv, dpos0, Bv, Tev, Sv, altv, vfn2 = vel
-            L.paig_head_bwd_vel_vfn2(ptr(S["h2"]), ptr(S["h3"]), ptr(denc), ptr(self.p("encoder.l3.weight")),
-                                     ptr(dh2), ptr(hslab), F, K, 200, float(H / 2), ptr(dXv), ptr(dpos0), Bv, Tev,
-                                     Sv, altv, *vfn2, st)
-        elif vel is not None:   # + the velocity encoder's input gradient (dXv, dpos0, B, Te, S, alt)
-            dXv, dpos0, Bv, Tev, Sv, altv, _ = vel
-            L.paig_head_bwd_vel(ptr(S["h2"]), ptr(S["h3"]), ptr(denc), ptr(self.p("encoder.l3.weight")), ptr(dh2),
-                                ptr(hslab), F, K, 200, float(H / 2), ptr(dXv), ptr(dpos0), Bv, Tev, Sv, altv, st)
+            L.paig_head_l2_bwd(*head, *(vel or _NO_VEL), ptr(self.p("encoder.l2.weight")), ptr(S.h1), ptr(dh1),
+                               *(vfn2 or _NO_VFN2), st)
+        elif vfn2 is not None:
+            L.paig_head_bwd_vel_vfn2(*head, *vel, *vfn2, st)
+        elif vel is not None:
+            L.paig_head_bwd_vel(*head, *vel, st)
         else:
-            L.paig_head_bwd(ptr(S["h2"]), ptr(S["h3"]), ptr(denc), ptr(self.p("encoder.l3.weight")), ptr(dh2),
-                            ptr(hslab), F, K, 200, float(H / 2), st)
+            L.paig_head_bwd(*head, st)
         g3 = self.g("encoder.l3.weight")
         assert self.g("encoder.l3.bias").data_ptr() == g3.data_ptr() + 400 * 4, "l3 grads not contiguous"
-        S["extra_slabs"].append((hslab, hblk, 402, g3))
+        S.extra_slabs.append((hslab, hblk, 402, g3))
         dobjs = _empty(K * F * lay.l1_in, dev)
         # l2's weight-gradient epilogue rides in l1's weight-gradient launch, and
         # l1's in l1's data-gradient launch (neither reads the deferred output;
         # l1's weight gradient takes the workspace past l2's partial slabs).
         # PAIG_GEMM_EPI_MERGE=0: separate epilogue launches (the A/B)
-        merge = os.environ.get("PAIG_GEMM_EPI_MERGE", "1") != "0" and not self.probe
+        merge = S.sw.gemm_epi_merge and not self.probe
         w2 = int(L.paig_gemm_workspace(200, 200, K * F)) if merge else 0
-        self.linear_bwd(S["h1"], dh2, K * F, "encoder.l2", dh1, S["h1"], 1, st, ws, need_dx=not fused_l2,
+        self.linear_bwd(S.h1, dh2, K * F, "encoder.l2", dh1, S.h1, 1, st, ws, need_dx=not fused_l2,
                         defer_epi=merge)
-        self.linear_bwd(S["l1_x"], dh1, K * F, "encoder.l1", dobjs, None, 0, st, ws[w2:] if merge else ws,
+        self.linear_bwd(S.l1_x, dh1, K * F, "encoder.l1", dobjs, None, 0, st, ws[w2:] if merge else ws,
                         defer_epi=merge)
         if merge:
             L.paig_gemm_flush(st)
@@ -913,8 +930,7 @@ class Engine:
 
         # ---- mask softmax backward (incl. ReLU' of ShallowUNet's c13, Q13, and
         # the AvgPool2d backward of the UNet path)
-        acts = S["acts"]
-        if S.get("head_fused"):
+        if S.head_in is not None:
             # fused head + softmax backward: the head input's dY (its
             # producer's ReLU' applied), written straight into the U-Net
             # workspace's gradient buffer, and the head's weight/bias partials
@@ -924,25 +940,18 @@ class Engine:
             nb = L.paig_head_mask_blocks(F, H, H)
             nw = K * c + K
             hs = _empty(nb * nw, dev)
-            L.paig_head_mask_bwd_ex(ptr(acts["head"]), ptr(self.p(hn + ".weight")), ptr(self.p(hn + ".bias")),
-                                    *x_view, ptr(S["masks"]), ptr(dobjs), ptr(dXl), ptr(hs), F, K, c, H, H,
+            L.paig_head_mask_bwd_ex(ptr(S.head_in), ptr(self.p(hn + ".weight")), ptr(self.p(hn + ".bias")),
+                                    *x_view, ptr(S.masks), ptr(dobjs), ptr(dXl), ptr(hs), F, K, c, H, H,
                                     lay.head_flags, st)
             gh = self.g(hn + ".weight")
             assert self.g(hn + ".bias").data_ptr() == gh.data_ptr() + K * c * 4, "head grads not contiguous"
-            S["extra_slabs"].append((hs, nb, nw, gh))
+            S.extra_slabs.append((hs, nb, nw, gh))
             self._unet_backward(S, None, st)
         else:
             dLG = _empty(F * K * HW, dev)
-            L.paig_mask_softmax_bwd(ptr(acts["LG"]), x_view[0], x_view[1], x_view[2], x_view[3], ptr(S["masks"]),
-                                    ptr(dobjs), ptr(dLG), F, K, 3, H, H,
+            L.paig_mask_softmax_bwd(ptr(S.logits), *x_view, ptr(S.masks), ptr(dobjs), ptr(dLG), F, K, 3, H, H,
                                     (1 if lay.lg_relu else 0) | (2 if lay.unet else 0), st)
             self._unet_backward(S, dLG, st)
-
-    @staticmethod
-    def _check_fresh(S):
-        if S.get("consumed"):
-            raise PaigError("a second backward through one forward (retain_graph=True) is not supported: the "
-                            "forward's saved state (its U-Net workspace) was released by the first backward")
 
     def _unet_backward(self, S, dlogits, st):
         """The U-Net backward (paig_unet_bwd_ex, the same C interpreter as the
@@ -950,8 +959,8 @@ class Engine:
         gradient already in the workspace; every conv's weight and bias
         gradient, with the step's other partial-gradient slabs (extra_slabs:
         head, l3, velocity MLP) in one batched deterministic reduction."""
-        self._check_fresh(S)
-        lay = S["lay"]
+        S.check_fresh()
+        lay = S.lay
         L = self.L
         Ws = [self.p(lay.prefix + f"c{c + 1}.weight") for c in range(lay.nconv)]
         dwb = []
@@ -960,13 +969,13 @@ class Engine:
             assert self.g(lay.prefix + f"c{c + 1}.bias").data_ptr() == gw.data_ptr() + gw.numel() * 4, \
                 "flat grads: weight and bias must be adjacent"
             dwb.append(ptr(gw))
-        extra = S.get("extra_slabs", [])
+        extra = S.extra_slabs
         n = len(extra)
-        ws = S["unet_ws"]
-        _, wpd = S["unet_wp"]
-        L.paig_unet_bwd_ex(lay.net, lay.F, lay.H, lay.K, S["cm"], S["unet_flags"], *S["x_view"],
-                           _parr([ptr(t) for t in Ws]), ptr(S["acts"].get("LG")), ptr(dlogits), _parr(dwb), n,
+        ws = S.unet_ws
+        _, wpd = S.unet_wp
+        L.paig_unet_bwd_ex(lay.net, lay.F, lay.H, lay.K, S.cm, S.unet_flags, *S.x_view,
+                           _parr([ptr(t) for t in Ws]), ptr(S.logits), ptr(dlogits), _parr(dwb), n,
                            _parr([ptr(e[0]) for e in extra]), _iarr([e[1] for e in extra]),
                            _iarr([e[2] for e in extra]), _parr([ptr(e[3]) for e in extra]), wpd, ptr(ws), ws.numel(),
                            self._unet_probe(S), None, st)
-        self._release(S)
+        S.release()

@@ -318,39 +318,35 @@ class _Encoder(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, anchor, model, which, need_saved=True):
-        from paig_reproduction_amd.engine import Layout, _empty
+        from paig_reproduction_amd.engine import Layout, read_switches
         x = _f32(x)
         N = x.shape[0]
         H = model.conv_input_shape[1]
         assert tuple(x.shape[1:]) == (3, H, H), (tuple(x.shape), H)
         eng = model._native()
         net = "unet" if which == "unet" else ("shallow_unet" if which == "shallow_unet" else None)
-        lay = Layout(model, N, 1, frames=N, net=net)
-        dev = x.device
-        st = stream_handle(dev)
-        ws = _empty(eng.workspace_floats(lay), dev)
+        lay = Layout(model, N, 1, read_switches(), frames=N, net=net)
+        st = stream_handle(x.device)
         # need_saved False (no autograd graph): the U-Net workspace without
         # gradient buffers, slabs or pool codes (PAIG_UNET_INFERENCE)
-        S = {"lay": lay, "x": x, "ws": ws, "dev": dev, "cm": eng.conv_flags(), "need_saved": need_saved}
-        x_view = (ptr(x), lay.frame, 0, 0)
+        S = eng.new_state(lay, x, need_saved)
         ctx.model, ctx.S, ctx.which = model, S, which
         if which == "encoder":
-            eng._encoder_forward(S, lay, x_view, ws, st)
-            K, HW = lay.K, lay.HW
-            masks = S["masks"].view(N, K + 1, H, H)
-            objs = S["objs"].view(K, N, 3, H, H)
+            eng._encoder_forward(S, st)
+            K = lay.K
+            masks = S.masks.view(N, K + 1, H, H)
+            objs = S.objs.view(K, N, 3, H, H)
             ctx.mark_non_differentiable(masks, objs)
-            return S["enc_pos"].view(N, 2 * K), masks, objs
-        S["x_view"] = x_view
-        eng._unet_forward(S, lay, x_view, st)
-        return S["acts"]["LG"].view(N, lay.K, H, H).clone()
+            return S.enc_pos.view(N, 2 * K), masks, objs
+        eng._unet_forward(S, st)
+        return S.logits.view(N, lay.K, H, H).clone()
 
     @staticmethod
     def backward(ctx, *grads):
         model, S, which = ctx.model, ctx.S, ctx.which
         eng = model._native()
-        lay = S["lay"]
-        st = stream_handle(S["dev"])
+        lay = S.lay
+        st = stream_handle(S.dev)
         if which == "encoder":
             denc = grads[0]
             if denc is None:

@@ -20,7 +20,7 @@ import torch
 import torch.nn as pnn
 
 from paig_reproduction_amd._lib import lib, ptr, stream_handle, require_device
-from paig_reproduction_amd.engine import Engine
+from paig_reproduction_amd.engine import Engine, LossAdjoints, live_steps, materialise
 from paig_reproduction_amd.flat import FlatParams
 from paig_reproduction_amd.nn.network.base import OPTIMIZERS, BaseNetTorch
 from paig_reproduction_amd.nn.network.blocks import ConvolutionalEncoder, VelocityEncoder, VariableFromNetwork
@@ -47,8 +47,8 @@ COORD_UNITS = {
 class _LossHandoff:
     """What the _LossReduce backwards of ONE forward leave for that forward's
     _PhysicsStep.backward: per SSE output (reconstruction / rollout frames) a
-    list of (in_kernel, (dt, de, dr, ae, B, Te, R, pred)), one entry per
-    compute_loss() whose loss reached the backward.  It lives on the forward's
+    list of (in_kernel, LossAdjoints), one entry per compute_loss() whose
+    loss reached the backward.  It lives on the forward's
     autograd context, so another model, another forward or an earlier backward
     can neither overwrite nor outlive it."""
     __slots__ = ("rec", "roll")
@@ -67,10 +67,8 @@ def _materialise_lossw(entries, mode, dev):
     rare paths: several losses on one forward, or a user gradient on the
     public SSE as well): one paig_loss_bwd per entry, summed."""
     w = None
-    for _, (dt, de, dr, ae, B, Te, R, pred) in entries:
-        wi = torch.empty(B * (Te if mode == 1 else R), device=dev)
-        lib().paig_loss_bwd(ptr(dt), ptr(de), ptr(dr), ae, ptr(wi) if mode == 1 else None,
-                            ptr(wi) if mode == 2 else None, B, Te, R, pred, stream_handle(dev))
+    for _, adj in entries:
+        wi = materialise(adj, mode, dev)
         w = wi if w is None else w + wi
     return w
 
@@ -126,15 +124,8 @@ class _PhysicsStep(torch.autograd.Function):
         ent_rec, ent_roll = ctx.hand.take()
         flat = ctx.engine.model._flat
         acc = flat.begin_backward()
-        # no extrapolation loss in the graph: only the first pred steps of
-        # every sequence carry a weight (physics_models.py:129-139), so the
-        # rollout decoder backward walks those frames only.  Decided afresh in
-        # every backward from what reached THIS forward: every loss on its
-        # rollout SSE came through compute_loss without an extrapolation
-        # adjoint, and nothing else (public SSE, dense frames) has a gradient.
-        live = 0
-        if d_out is None and d_sse_roll is None and ent_roll and all(lw[1] is None for _, lw in ent_roll):
-            live = ent_roll[0][1][7]
+        # decided afresh in every backward from what reached THIS forward
+        live = live_steps(d_out, d_sse_roll, ent_roll)
         w_rec, lw_rec = _PhysicsStep._weights(d_sse_rec, d_priv_rec, ent_rec, 1)
         w_roll, lw_roll = _PhysicsStep._weights(d_sse_roll, d_priv_roll, ent_roll, 2)
         # incoming gradients may be broadcast views (d sum(sse)/d sse is an
@@ -189,7 +180,7 @@ class _LossReduce(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dt, de, dr):
         B, Te, R, pred, ae = ctx.shape
-        lw = (dt, de, dr, ae, B, Te, R, pred)
+        lw = LossAdjoints(dt, de, dr, ae, B, Te, R, pred)
         # in-kernel: the per-frame weights are formed inside the decoder
         # backwards from these adjoints (paig_decoder_bwd_ex lw modes).  The
         # adjoints travel on the forward's hand-off; the returned gradient is
