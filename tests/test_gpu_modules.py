@@ -159,12 +159,35 @@ def test_velocity_encoder(name):
     assert rel_err(pi.grad, pr.grad) <= RT
 
 
-@pytest.mark.parametrize("name", ["spring_s12", "bouncing_s12", "3bp_s20"])
+def _acting_states(cell, state):
+    """9 states at which the cell's physics acts (tests/rollout_cases.py's
+    recipes, margins asserted under the fixture's own dt and parameters):
+    bouncing states whose step hits a wall, gravity bodies 3+ px apart (the
+    unclamped force), spring ends near the rest length.  The fixtures' first
+    states never bounce and keep the three bodies inside both clamps."""
+    import rollout_cases as C
+    dt = state["rollout_cell.dt"]
+    if cell == "bouncing_ode_cell":
+        pos, vel = C.bouncing_wall_states(9)
+        rep = C.assert_margins(C.BOUNCE, pos, vel, 1, dt=dt)
+        assert bool(((rep["up"] + rep["low"]).sum(1) > 0).all())
+    elif cell == "gravity_ode_cell":
+        pos, vel, _ = C.gravity_inputs("free", 9, 1)
+        C.assert_margins(C.GRAVITY, pos, vel, 1, "free", dt=dt,
+                         prm={"g": state["rollout_cell.g"], "m": state["rollout_cell.m"]})
+    else:
+        pos, vel = C.spring_inputs(9, 1)[:2]
+    return pos, vel
+
+
+@pytest.mark.parametrize("name", ["spring_s12", "bouncing_s12", "3bp_s20",
+                                  "spring_s12+acting", "bouncing_s12+acting", "3bp_s20+acting"])
 def test_ode_cell(name):
+    name, _, acting = name.partition("+")
     z, cfg, state, m, x = _setup(name)
     pv = torch.from_numpy(np.asarray(z["pos_vel_seq"])[:, 0].copy())
     D = cfg.D
-    pos, vel = pv[:, :D], pv[:, D:]
+    pos, vel = _acting_states(cfg.cell, state) if acting else (pv[:, :D], pv[:, D:])
     pg, vg = pos.to(DEV).requires_grad_(True), vel.to(DEV).requires_grad_(True)
     p1, v1 = m.rollout_cell(pg, vg)
     keys = {"spring_ode_cell": ["rollout_cell.k", "rollout_cell.equil"], "gravity_ode_cell": ["rollout_cell.g"],
