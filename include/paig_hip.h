@@ -31,7 +31,7 @@ extern "C" {
 /* Version of this interface: bumped whenever an entry point's argument list
  * or a data layout it exchanges changes (the Python binding refuses a library
  * of another version). */
-#define PAIG_ABI_VERSION 9
+#define PAIG_ABI_VERSION 10
 const char* paig_last_error(void);
 int paig_abi_version(void);
 /* f16 range guard of the split-precision path.  Activations and gradients
@@ -568,6 +568,48 @@ int paig_decoder_bwd_t8(const float* pos, long long pos_outer, long long pos_inn
                         long long tgt_fs, int tgt_grp, long long tgt_gs, const float* dsse, const float* dout,
                         long long dout_fs, float* dpos, float* slab, float* scratch, int F, int live, int K, int h,
                         int H, void* stream);
+
+/* ---- the attention-window scale sigma (physics_models.py:155-162, "This
+ *      parameter can be played with"): sigma = np.exp(np.log(log_sig)).  The
+ *      warp of object k becomes theta = [[s,0,t2],[0,s,t5]] with theta0 =
+ *      theta4 = sigma in fp64 (:160-162) and t2 = fl32((H/2 - x)/tmpl) *
+ *      fl32(sigma), t5 likewise, in fp32 (:166-167); the grid is formed in
+ *      fp64 (the stack promotes theta) and cast to fp32 (stn.py:12-14), and
+ *      the position gradient picks up the factor fl32(sigma).  sigma in
+ *      [0.5, 2], an error outside (no clamping); the entry points above are
+ *      these with sigma = 1.  Each mirrors its namesake's arguments, sigma
+ *      before the stream.
+ *      The backward of the one-CU shapes runs the one-CU kernels for sigma in
+ *      [1, 2] (a source texel gathers <= 5 output indices per axis) and the
+ *      generic kernels for sigma in [0.5, 1) (up to 9), with every target /
+ *      loss-weight / live mode on both; so the slab rows and the scratch
+ *      depend on sigma (paig_decoder_slab_len does not). */
+int paig_decoder_fwd_sigma(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
+                           const float* cont, const float* bg, float* out, long long out_fs, const float* tgt,
+                           long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H,
+                           double sigma, void* stream);
+int paig_decoder_fwd_rollout_sigma(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
+                                   const double* p0, const double* p1, float* pvs, int B, int D, int R,
+                                   const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                                   const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
+                                   const float* tgt, long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F,
+                                   int K, int h, int H, double sigma, void* stream);
+int paig_decoder_fwd_t8_sigma(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                              const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
+                              const unsigned char* tgt, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
+                              long long tgt_gs, float* sse, int F, int K, int h, int H, double sigma, void* stream);
+int paig_decoder_bwd_blocks_sigma(int F, int pos_grp, int live, int K, int h, int H, double sigma);
+size_t paig_decoder_bwd_scratch_sigma(int F, int K, int h, int H, double sigma);
+int paig_decoder_bwd_ex_sigma(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                              const float* tmpl, const float* cont, const float* bg, const float* tgt,
+                              const unsigned char* tgt8, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
+                              long long tgt_gs, const float* dsse, int lw_mode, const float* dt, const float* de,
+                              const float* dr, float ae, int lB, int lTe, int lR, int lpred, const float* dout,
+                              long long dout_fs, float* dpos, float* slab, float* scratch, int F, int live, int K,
+                              int h, int H, double sigma, void* stream);
+int paig_decoder_parts_sigma(const float* pos, long long pos_inner, const float* tmpl, const float* cont,
+                             const float* bg, float* contents, float* masks, int F, int K, int h, int H, double sigma,
+                             void* stream);
 
 /* the decoder's per-object intermediates (transf_contents / transf_masks,
  * physics_models.py:186-196) for positions pos [F][2K] (row stride

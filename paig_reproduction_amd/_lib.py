@@ -17,7 +17,7 @@ XMAX_SLOTS = 2048
 
 AB_PATH = os.environ.get("PAIG_AB_LIB")
 # include/paig_hip.h PAIG_ABI_VERSION: the SIGNATURES below are this version's
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -127,6 +127,15 @@ SIGNATURES = {
                                  I, I, I, I, I, P]),
     "paig_decoder_bwd_t8": (I, [P, LL, LL, I, P, P, P, P, P, LL, I, LL, P, P, LL, P, P, P, I, I, I, I, I, P]),
     "paig_decoder_parts": (I, [P, LL, P, P, P, P, P, I, I, I, I, P]),
+    "paig_decoder_fwd_sigma": (I, [P, LL, LL, I, P, P, P, P, LL, P, LL, I, LL, P, I, I, I, I, F64, P]),
+    "paig_decoder_fwd_rollout_sigma": (I, [I, P, LL, P, P, P, P, P, I, I, I, P, LL, LL, I, P, P, P, P, LL, P, LL, I, LL,
+                                            P, I, I, I, I, F64, P]),
+    "paig_decoder_fwd_t8_sigma": (I, [P, LL, LL, I, P, P, P, P, LL, P, P, LL, I, LL, P, I, I, I, I, F64, P]),
+    "paig_decoder_bwd_blocks_sigma": (I, [I, I, I, I, I, I, F64]),
+    "paig_decoder_bwd_scratch_sigma": (SZ, [I, I, I, I, F64]),
+    "paig_decoder_bwd_ex_sigma": (I, [P, LL, LL, I, P, P, P, P, P, P, LL, I, LL, P, I, P, P, P, F32, I, I, I, I, P, LL, P,
+                                       P, P, I, I, I, I, I, F64, P]),
+    "paig_decoder_parts_sigma": (I, [P, LL, P, P, P, P, P, I, I, I, I, F64, P]),
     "paig_stn_fwd": (I, [P, P, P, I, I, I, I, I, I, P]),
     "paig_stn_bwd": (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
     "paig_stn_fwd_f64": (I, [P, P, P, I, I, I, I, I, I, P]),
@@ -155,7 +164,7 @@ _QUERY = {"paig_last_error", "paig_abi_version", "paig_f16_range_status", "paig_
           "paig_unet_buffer", "paig_unet_query", "paig_localiser_workspace",
           "paig_velmlp_rollout_bwd_workspace",
           "paig_vfn_bwd_blocks", "paig_rollout_bwd_blocks", "paig_decoder_bwd_blocks", "paig_decoder_slab_len",
-          "paig_decoder_bwd_scratch"}
+          "paig_decoder_bwd_scratch", "paig_decoder_bwd_blocks_sigma", "paig_decoder_bwd_scratch_sigma"}
 
 
 class PaigError(RuntimeError):

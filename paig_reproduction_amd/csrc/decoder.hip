@@ -40,6 +40,16 @@ struct PosView {
   const float* p;
   long long outer, inner;
   int grp;
+  // the attention-window scale sigma (physics_models.py:160-162): theta0 =
+  // theta4 = sg in fp64, and sgf = fl32(sigma), the scalar of the fp32
+  // products theta2, theta5 (:166-167)
+  double sg;
+  float sgf;
+  // theta2 / theta5 of an object at l on one axis: fp32 as the reference
+  // forms it, widened for the fp64 grid (Q9)
+  __device__ __forceinline__ double theta_t(float l, int H, int h) const {
+    return (double)((((float)H / 2.f - l) / (float)h) * sgf);
+  }
   __device__ __forceinline__ const float* at(int f) const {
     return grp > 0 ? p + (long long)(f / grp) * outer + (long long)(f % grp) * inner : p + (long long)f * inner;
   }
@@ -54,8 +64,8 @@ __device__ __forceinline__ double base_coord(int j, int n) {
 
 // grid_sample unnormalized source coordinate for output index j, from the
 // block's table of base coordinates bc[j] = base_coord(j, n)
-__device__ __forceinline__ float src_coord(double bcj, double t, int h) {
-  const float g = (float)(bcj + t);
+__device__ __forceinline__ float src_coord(double bcj, double t, int h, double sg) {
+  const float g = (float)(sg * bcj + t);
   return ((g + 1.f) * (float)h - 1.f) / 2.f;
 }
 
@@ -93,14 +103,15 @@ __device__ __forceinline__ void sample(const float* s, int h, const Bil& b, floa
 // per (frame, object, row/col) instead of per pixel.  Caller syncs.
 constexpr int MAXH = 64;
 template <int K>
-__device__ __forceinline__ void coord_tables(const float* pf, int H, int h, float (*cx)[MAXH], float (*cy)[MAXH],
-                                             const double* bc) {
+__device__ __forceinline__ void coord_tables(const PosView& pos, int f, int H, int h, float (*cx)[MAXH],
+                                             float (*cy)[MAXH], const double* bc) {
+  const float* pf = pos.at(f);
   for (int t = threadIdx.x; t < K * 2 * H; t += blockDim.x) {
     const int k = t / (2 * H), r = t % (2 * H);
     const float l = r < H ? pf[2 * k] : pf[2 * k + 1];
-    const double tt = (double)(((float)H / 2.f - l) / (float)h);
-    if (r < H) cx[k][r] = src_coord(bc[r], tt, h);
-    else cy[k][r - H] = src_coord(bc[r - H], tt, h);
+    const double tt = pos.theta_t(l, H, h);
+    if (r < H) cx[k][r] = src_coord(bc[r], tt, h, pos.sg);
+    else cy[k][r - H] = src_coord(bc[r - H], tt, h, pos.sg);
   }
 }
 
@@ -170,7 +181,7 @@ dec_fwd_k(PosView pos, Src S, FViewW out, FView tgt, float* __restrict__ sse, in
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int f = blockIdx.x; f < F; f += gridDim.x) {
     __syncthreads();   // previous frame done with the tables
-    coord_tables<K>(pos.at(f), H, h, cx, cy, bc);
+    coord_tables<K>(pos, f, H, h, cx, cy, bc);
     __syncthreads();
     float* of = out.frame(f);
     const float* tf = sse ? tgt.frame(f) : nullptr;
@@ -205,155 +216,7 @@ dec_fwd_k(PosView pos, Src S, FViewW out, FView tgt, float* __restrict__ sse, in
   }
 }
 
-// slab row layout per block: [K*h*h template | K*3*h*h content | 3*H*W bg]
-template <int K>
-__global__ void __launch_bounds__(256)
-dec_bwd_k(PosView pos, Src S, FView tgt, const float* __restrict__ dsse, FView dout, float* __restrict__ dpos,
-          float* __restrict__ slab, float* __restrict__ gscratch, int F, int h, int H) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int hh = h * h, HW = H * H;
-  float* T = lds;
-  float* Cn = T + K * hh;
-  float* G = gscratch ? gscratch + (long long)blockIdx.x * K * 4 * HW : Cn + K * 3 * hh;  // [K][4][HW]
-  __shared__ double redd[4][2 * K];
-  __shared__ int skip_s;
-  __shared__ float cx[K][MAXH], cy[K][MAXH];
-  __shared__ double bc[MAXH];
-  init_base(bc, H);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int nw = blockDim.x >> 6;
-  const long long slab_len = (long long)K * hh + (long long)K * 3 * hh + 3LL * HW;
-  float* srow = slab + (long long)blockIdx.x * slab_len;
-  float* s_tm = srow;
-  float* s_ct = srow + K * hh;
-  float* s_bg = s_ct + K * 3 * hh;
-  // zero this block's slab row (each element is owned by exactly one thread below)
-  for (int s = threadIdx.x; s < K * hh; s += blockDim.x) {
-    s_tm[s] = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) s_ct[(s / hh * 3 + c) * hh + s % hh] = 0.f;
-  }
-  for (int p = threadIdx.x; p < HW; p += blockDim.x)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) s_bg[c * HW + p] = 0.f;
-  stage_sources<K>(S, h, T, Cn);
-  __syncthreads();
-
-  for (int f = blockIdx.x; f < F; f += gridDim.x) {
-    const float w_f = dsse ? 2.f * dsse[f] : 0.f;
-    const float* dof = dout.p ? dout.frame(f) : nullptr;
-    if (threadIdx.x == 0) skip_s = (w_f == 0.f && dof == nullptr);
-    __syncthreads();
-    if (skip_s) {
-      if (threadIdx.x < 2 * K) dpos[(long long)f * 2 * K + threadIdx.x] = 0.f;
-      __syncthreads();
-      continue;
-    }
-    coord_tables<K>(pos.at(f), H, h, cx, cy, bc);
-    __syncthreads();
-    const float* tf = tgt.frame(f);
-    double sx[K], sy[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) sx[k] = sy[k] = 0.0;
-
-    // ---- pass 1: per-pixel gradients
-    for (int p = threadIdx.x; p < HW; p += blockDim.x) {
-      const int i = p / H, j = p % H;
-      Bil bl[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) bl[k] = bil(cx[k][j], cy[k][i]);
-      float o[3], m[K + 1], cs[K][3];
-      composite<K>(T, Cn, S.bg, HW, p, h, bl, o, m, cs);
-      float g[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        g[c] = w_f * (o[c] - tf[c * HW + p]);
-        if (dof) g[c] += dof[c * HW + p];
-        s_bg[c * HW + p] += m[K] * g[c];
-      }
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        float dT = 0.f;
-        float dC[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          dC[c] = m[k] * g[c];
-          dT = fmaf(g[c], cs[k][c] - o[c], dT);
-        }
-        dT *= m[k];
-        G[(k * 4 + 0) * HW + p] = dT;
-        float v, dx, dy;
-        sample(T + k * hh, h, bl[k], v, dx, dy);
-        float gx = dT * dx, gy = dT * dy;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          G[(k * 4 + 1 + c) * HW + p] = dC[c];
-          sample(Cn + (k * 3 + c) * hh, h, bl[k], v, dx, dy);
-          gx = fmaf(dC[c], dx, gx);
-          gy = fmaf(dC[c], dy, gy);
-        }
-        sx[k] += (double)gx;
-        sy[k] += (double)gy;
-      }
-    }
-    // ---- per-frame dpos reduction (fp64)
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      double a = wave_sum_d(sx[k]), b = wave_sum_d(sy[k]);
-      if (lane == 0) {
-        redd[wv][2 * k] = a;
-        redd[wv][2 * k + 1] = b;
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * K) {
-      double s = 0.0;
-      for (int w = 0; w < nw; ++w) s += redd[w][threadIdx.x];
-      // d theta = sum_p dgrid = sum_p dix * h/2 ; dloc = -dtheta / h
-      const float dth = (float)(s * (double)h * 0.5);
-      dpos[(long long)f * 2 * K + threadIdx.x] = -dth / (float)h;
-    }
-    // ---- pass 2: gather source gradients from the pixel-gradient image
-    for (int s = threadIdx.x; s < K * hh; s += blockDim.x) {
-      const int k = s / hh, q = s % hh, ys = q / h, xs = q % h;
-      // output index j has ix(j) ~= a + j*h/H; candidates with floor(ix) in {xs-1, xs}
-      const float a0x = cx[k][0], a0y = cy[k][0];
-      const float slope = (float)h / (float)H;
-      int jlo = (int)floorf(((float)xs - 1.f - a0x) / slope) - 1, jhi = (int)ceilf(((float)xs + 1.f - a0x) / slope) + 1;
-      int ilo = (int)floorf(((float)ys - 1.f - a0y) / slope) - 1, ihi = (int)ceilf(((float)ys + 1.f - a0y) / slope) + 1;
-      if (jlo < 0) jlo = 0;
-      if (ilo < 0) ilo = 0;
-      if (jhi > H - 1) jhi = H - 1;
-      if (ihi > H - 1) ihi = H - 1;
-      float acc[4] = {0.f, 0.f, 0.f, 0.f};
-      for (int i = ilo; i <= ihi; ++i) {
-        const float iy = cy[k][i];
-        const float fy0 = floorf(iy);
-        const int y0 = (int)fy0;
-        const float fy = iy - fy0;
-        const float wy = (y0 == ys ? 1.f - fy : 0.f) + (y0 + 1 == ys ? fy : 0.f);
-        if (wy == 0.f) continue;
-        float row[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int j = jlo; j <= jhi; ++j) {
-          const float ix = cx[k][j];
-          const float fx0 = floorf(ix);
-          const int x0 = (int)fx0;
-          const float fx = ix - fx0;
-          const float wx = (x0 == xs ? 1.f - fx : 0.f) + (x0 + 1 == xs ? fx : 0.f);
-          if (wx == 0.f) continue;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) row[c] = fmaf(wx, G[(k * 4 + c) * HW + i * H + j], row[c]);
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[c] = fmaf(wy, row[c], acc[c]);
-      }
-      s_tm[s] += acc[0];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) s_ct[(k * 3 + c) * hh + q] += acc[1 + c];
-    }
-    __syncthreads();
-  }
-}
+// (the generic backward, dec_bwd_k, follows the target / loss-weight views below)
 
 // ---------------------------------------------------------------------------
 // Register-resident forward for the small frames of the headline workloads
@@ -482,7 +345,7 @@ dec_fwd_reg_k(PosView pos, Src S, FViewW out, FView tgt, float* __restrict__ sse
   if (sse && (int)blockIdx.x < F) fetch(blockIdx.x);
   for (int f = blockIdx.x; f < F; f += gridDim.x) {
     __syncthreads();   // previous frame done with the tables
-    coord_tables<K>(pos.at(f), H, h, cx, cy, bc);
+    coord_tables<K>(pos, f, H, h, cx, cy, bc);
     __syncthreads();
     float tc[PPT][3];
 #pragma unroll
@@ -525,21 +388,26 @@ dec_fwd_reg_k(PosView pos, Src S, FViewW out, FView tgt, float* __restrict__ sse
 // 5-wide window of output columns (rows) and their bilinear weights on s
 // (nonzero where floor(c[j]) == s: 1 - frac, or floor(c[j]) + 1 == s: frac;
 // c[j] = the sample coordinate of output index j, as coord_tables() forms
-// it from the fp64 base coordinates bc[]).  With the 2x upsampling warp at
-// most 4 output indices contribute (5 with rounding at both ends).  The
-// coordinates are evaluated directly (no scan over a coordinate table): c is
-// j/2 + c[0] up to fp32 rounding (~1e-6), so the first j with floor(c[j]) >=
-// s-1 is one of three candidates around that estimate.
+// it from the fp64 base coordinates bc[]).  The warp's slope is sigma / 2
+// source texels per output index, so at most 4 / sigma output indices
+// contribute (one more with rounding at both ends): 5 for sigma >= 1, the
+// range these tables serve (sigma < 1 takes the generic backward, whose
+// window is sized per launch).  The coordinates are evaluated directly (no
+// scan over a coordinate table): c is j sigma/2 + c[0] up to fp32 rounding
+// (~1e-6), so the first j with floor(c[j]) >= s-1 is one of three candidates
+// around that estimate.
 constexpr int GW = 5;
-__device__ __forceinline__ void gather_entry(float l, const double* bc, int H, int h, int s, int* j0, float* wt) {
-  const double tt = (double)(((float)H / 2.f - l) / (float)h);
-  const float c0 = src_coord(bc[0], tt, h);
-  const int je = (int)ceilf(2.f * ((float)s - 1.f - c0)) - 1;
+__device__ __forceinline__ void gather_entry(const PosView& pos, float l, const double* bc, int H, int h, int s,
+                                             int* j0, float* wt) {
+  const double tt = pos.theta_t(l, H, h), sg = pos.sg;
+  const float c0 = src_coord(bc[0], tt, h, sg);
+  // the coordinate slope is sigma / 2 per output index
+  const int je = (int)ceilf((2.f / pos.sgf) * ((float)s - 1.f - c0)) - 1;
   int j = je;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     const int jj = je + i;
-    const float c = jj < 0 ? -1e30f : (jj >= H ? 1e30f : src_coord(bc[jj], tt, h));
+    const float c = jj < 0 ? -1e30f : (jj >= H ? 1e30f : src_coord(bc[jj], tt, h, sg));
     if (floorf(c) < (float)(s - 1)) j = jj + 1;
   }
   // the window stays inside [0, H): indices before the first contributor get
@@ -549,7 +417,7 @@ __device__ __forceinline__ void gather_entry(float l, const double* bc, int H, i
   *j0 = j;
 #pragma unroll
   for (int b = 0; b < GW; ++b) {
-    const float v = src_coord(bc[j + b], tt, h), f0 = floorf(v);
+    const float v = src_coord(bc[j + b], tt, h, sg), f0 = floorf(v);
     const int x0 = (int)f0;
     const float fr = v - f0;
     wt[b] = (x0 == s ? 1.f - fr : 0.f) + (x0 + 1 == s ? fr : 0.f);
@@ -804,6 +672,168 @@ struct DecFrames {
   }
 };
 
+// The generic backward (any H = 2h <= MAXH; the gather window of pass 2 is
+// sized from the launch's sigma, so it also serves the one-CU shapes at
+// sigma < 1, whose window is wider than the one-CU kernels' 5-wide tables).
+// Every frame is walked: the dead ones (step >= live of a group, or a zero
+// weight and no dense gradient) get zero position gradients and are not read.
+// Targets (T8) and loss weights (LW) as in the one-CU kernels.
+// slab row layout per block: [K*h*h template | K*3*h*h content | 3*H*W bg]
+template <int K, bool T8, bool LW>
+__global__ void __launch_bounds__(256)
+dec_bwd_k(PosView pos, Src S, TView tgt, WSrc dsse, FView dout, float* __restrict__ dpos,
+          float* __restrict__ slab, float* __restrict__ gscratch, int F, int live, int h, int H) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int hh = h * h, HW = H * H;
+  float* T = lds;
+  float* Cn = T + K * hh;
+  float* G = gscratch ? gscratch + (long long)blockIdx.x * K * 4 * HW : Cn + K * 3 * hh;  // [K][4][HW]
+  __shared__ double redd[4][2 * K];
+  __shared__ int skip_s;
+  __shared__ float cx[K][MAXH], cy[K][MAXH];
+  __shared__ double bc[MAXH];
+  init_base(bc, H);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int nw = blockDim.x >> 6;
+  const long long slab_len = (long long)K * hh + (long long)K * 3 * hh + 3LL * HW;
+  float* srow = slab + (long long)blockIdx.x * slab_len;
+  float* s_tm = srow;
+  float* s_ct = srow + K * hh;
+  float* s_bg = s_ct + K * 3 * hh;
+  // zero this block's slab row (each element is owned by exactly one thread below)
+  for (int s = threadIdx.x; s < K * hh; s += blockDim.x) {
+    s_tm[s] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s_ct[(s / hh * 3 + c) * hh + s % hh] = 0.f;
+  }
+  for (int p = threadIdx.x; p < HW; p += blockDim.x)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s_bg[c * HW + p] = 0.f;
+  stage_sources<K>(S, h, T, Cn);
+  const DecFrames FR(pos, tgt, 0);
+  const bool has_w = dsse.template has<LW>();
+  dsse.template prep<LW>();
+  __syncthreads();
+
+  for (int f = blockIdx.x; f < F; f += gridDim.x) {
+    const DecCursor cur = FR.at(f);
+    const bool dead = live > 0 && cur.pr >= live;
+    const float w_f = has_w && !dead ? 2.f * dsse.template at<LW>(cur) : 0.f;
+    const float* dof = dout.p ? dout.frame(f) : nullptr;
+    if (threadIdx.x == 0) skip_s = (w_f == 0.f && dof == nullptr);
+    __syncthreads();
+    if (skip_s) {
+      if (threadIdx.x < 2 * K) dpos[(long long)f * 2 * K + threadIdx.x] = 0.f;
+      __syncthreads();
+      continue;
+    }
+    coord_tables<K>(pos, f, H, h, cx, cy, bc);
+    __syncthreads();
+    const long long to = has_w ? FR.template tgt_off<T8>(cur) : 0;
+    double sx[K], sy[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) sx[k] = sy[k] = 0.0;
+
+    // ---- pass 1: per-pixel gradients
+    for (int p = threadIdx.x; p < HW; p += blockDim.x) {
+      const int i = p / H, j = p % H;
+      Bil bl[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) bl[k] = bil(cx[k][j], cy[k][i]);
+      float o[3], m[K + 1], cs[K][3];
+      composite<K>(T, Cn, S.bg, HW, p, h, bl, o, m, cs);
+      float g[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float tv = has_w ? TView::val1<T8>(tgt.template raw1<T8>(to + c * HW + p)) : 0.f;
+        g[c] = w_f * (o[c] - tv);
+        if (dof) g[c] += dof[c * HW + p];
+        s_bg[c * HW + p] += m[K] * g[c];
+      }
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        float dT = 0.f;
+        float dC[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          dC[c] = m[k] * g[c];
+          dT = fmaf(g[c], cs[k][c] - o[c], dT);
+        }
+        dT *= m[k];
+        G[(k * 4 + 0) * HW + p] = dT;
+        float v, dx, dy;
+        sample(T + k * hh, h, bl[k], v, dx, dy);
+        float gx = dT * dx, gy = dT * dy;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          G[(k * 4 + 1 + c) * HW + p] = dC[c];
+          sample(Cn + (k * 3 + c) * hh, h, bl[k], v, dx, dy);
+          gx = fmaf(dC[c], dx, gx);
+          gy = fmaf(dC[c], dy, gy);
+        }
+        sx[k] += (double)gx;
+        sy[k] += (double)gy;
+      }
+    }
+    // ---- per-frame dpos reduction (fp64)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      double a = wave_sum_d(sx[k]), b = wave_sum_d(sy[k]);
+      if (lane == 0) {
+        redd[wv][2 * k] = a;
+        redd[wv][2 * k + 1] = b;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * K) {
+      double s = 0.0;
+      for (int w = 0; w < nw; ++w) s += redd[w][threadIdx.x];
+      // d theta = sum_p dgrid = sum_p dix * h/2 ; dloc = -(dtheta * sigma) / h
+      const float dth = (float)(s * (double)h * 0.5);
+      dpos[(long long)f * 2 * K + threadIdx.x] = -(dth * pos.sgf) / (float)h;
+    }
+    // ---- pass 2: gather source gradients from the pixel-gradient image
+    for (int s = threadIdx.x; s < K * hh; s += blockDim.x) {
+      const int k = s / hh, q = s % hh, ys = q / h, xs = q % h;
+      // output index j has ix(j) ~= a + j*sigma*h/H; candidates with floor(ix) in {xs-1, xs}
+      const float a0x = cx[k][0], a0y = cy[k][0];
+      const float slope = (float)h / (float)H * pos.sgf;
+      int jlo = (int)floorf(((float)xs - 1.f - a0x) / slope) - 1, jhi = (int)ceilf(((float)xs + 1.f - a0x) / slope) + 1;
+      int ilo = (int)floorf(((float)ys - 1.f - a0y) / slope) - 1, ihi = (int)ceilf(((float)ys + 1.f - a0y) / slope) + 1;
+      if (jlo < 0) jlo = 0;
+      if (ilo < 0) ilo = 0;
+      if (jhi > H - 1) jhi = H - 1;
+      if (ihi > H - 1) ihi = H - 1;
+      float acc[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int i = ilo; i <= ihi; ++i) {
+        const float iy = cy[k][i];
+        const float fy0 = floorf(iy);
+        const int y0 = (int)fy0;
+        const float fy = iy - fy0;
+        const float wy = (y0 == ys ? 1.f - fy : 0.f) + (y0 + 1 == ys ? fy : 0.f);
+        if (wy == 0.f) continue;
+        float row[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int j = jlo; j <= jhi; ++j) {
+          const float ix = cx[k][j];
+          const float fx0 = floorf(ix);
+          const int x0 = (int)fx0;
+          const float fx = ix - fx0;
+          const float wx = (x0 == xs ? 1.f - fx : 0.f) + (x0 + 1 == xs ? fx : 0.f);
+          if (wx == 0.f) continue;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) row[c] = fmaf(wx, G[(k * 4 + c) * HW + i * H + j], row[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = fmaf(wy, row[c], acc[c]);
+      }
+      s_tm[s] += acc[0];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) s_ct[(k * 3 + c) * hh + q] += acc[1 + c];
+    }
+    __syncthreads();
+  }
+}
+
 // separable bilinear setup of one axis: tap index (padded source), masked
 // weights of the two taps and their d/dcoord (0 for out-of-range taps)
 struct Ax {
@@ -930,11 +960,11 @@ dec_bwd_cu_k(PosView pos, Src S, TView tgt, WSrc dsse, FView dout, float* __rest
   // the tables of a frame from this thread's position value l (BC complete)
   auto tables = [&](float l, int aslot, int gslot_) {
     if (is_c) {
-      const Ax x = axis(src_coord(BC[cj], (double)(((float)H / 2.f - l) / (float)h), h), h);
+      const Ax x = axis(src_coord(BC[cj], pos.theta_t(l, H, h), h, pos.sg), h);
       AXW[aslot][ck][cax][cj] = make_float4(x.w0, x.w1, x.d0, x.d1);
       AXC[aslot][ck][cax][cj] = x.c;
     } else if (is_g) {
-      gather_entry(l, BC, H, h, cj, &J0[gslot_][ck][cax][cj], WT[gslot_][ck][cax][cj]);
+      gather_entry(pos, l, BC, H, h, cj, &J0[gslot_][ck][cax][cj], WT[gslot_][ck][cax][cj]);
     }
   };
   // targets -> tn (no SSE weight: none read); staged: the row from IXS, else
@@ -1035,7 +1065,7 @@ dec_bwd_cu_k(PosView pos, Src S, TView tgt, WSrc dsse, FView dout, float* __rest
           const double v = lane < NR ? RED[sl][wv][lane] : 0.0;
           const double tot = wave_sum_dpp_d(v);
           const float dth = (float)(tot * (double)h * 0.5);
-          if (lane == 0) dpos[(long long)cprev.f * 2 * K + wv] = -dth / (float)h;
+          if (lane == 0) dpos[(long long)cprev.f * 2 * K + wv] = -(dth * pos.sgf) / (float)h;
         }
   #pragma unroll
         for (int u = 0; u < NIT; ++u) {
@@ -1402,11 +1432,11 @@ dec_bwd_band_k(PosView pos, Src S, TView tgt, WSrc dsse, FView dout, float* __re
     if (is_c || is_g) {
       const float l = FR.pos_of(cur)[2 * ck + cax];
       if (is_c) {
-        const Ax x = axis(src_coord(BC[cj], (double)(((float)H / 2.f - l) / (float)h), h), h);
+        const Ax x = axis(src_coord(BC[cj], pos.theta_t(l, H, h), h, pos.sg), h);
         AXW[ck][cax][cj] = make_float4(x.w0, x.w1, x.d0, x.d1);
         AXC[ck][cax][cj] = x.c;
       } else {
-        gather_entry(l, BC, H, h, cj, &J0[ck][cax][cj], WT[ck][cax][cj]);
+        gather_entry(pos, l, BC, H, h, cj, &J0[ck][cax][cj], WT[ck][cax][cj]);
       }
     }
     __syncthreads();
@@ -1569,7 +1599,7 @@ dec_bwd_band_k(PosView pos, Src S, TView tgt, WSrc dsse, FView dout, float* __re
     if (wv < 2 * K) {   // wave e finishes position gradient e
       const double tot = wave_sum_dpp_d(lane < NR ? RED[wv][lane] : 0.0);
       const float dth = (float)(tot * (double)h * 0.5);
-      if (lane == 0) dpos[(long long)cur.f * 2 * K + wv] = -dth / (float)h;
+      if (lane == 0) dpos[(long long)cur.f * 2 * K + wv] = -(dth * pos.sgf) / (float)h;
     }
     gather(1);
     cur = nxt;
@@ -1703,7 +1733,7 @@ __device__ __forceinline__ void dec_fwd_cu_body(PosView pos, Src S, FViewW out, 
   for (int j = tid; j < H; j += C::NT) BC[j] = base_coord(j, H);
   auto tables = [&](float l, int slot) {
     if (is_c) {
-      const Ax x = axis(src_coord(BC[cj], (double)(((float)H / 2.f - l) / (float)h), h), h);
+      const Ax x = axis(src_coord(BC[cj], pos.theta_t(l, H, h), h, pos.sg), h);
       if (cax == 0)
         AXC[slot][ck][cj & 3][cj >> 2] =
             make_float4(x.w0, x.w1, __int_as_float(texel_slot(hp, x.c)), __int_as_float(texel_slot(hp, x.c + 1)));
@@ -1908,7 +1938,7 @@ dec_parts_k(PosView pos, Src S, float* __restrict__ contents, float* __restrict_
   const long long plane = (long long)F * 3 * HW;   // one [F][3][H][W] tensor
   for (int f = blockIdx.x; f < F; f += gridDim.x) {
     __syncthreads();
-    coord_tables<K>(pos.at(f), H, h, cx, cy, bc);
+    coord_tables<K>(pos, f, H, h, cx, cy, bc);
     __syncthreads();
     for (int p = threadIdx.x; p < HW; p += blockDim.x) {
       const int i = p / H, j = p % H;
@@ -2062,11 +2092,20 @@ static int dec_cu_fpb(int NL) {
   return fpb < fmin ? fmin : fpb;
 }
 
-// Slab rows (= blocks) of paig_decoder_bwd over F frames grouped by grp
+// The supported attention-window scales (physics_models.py:155-162); no
+// clamping outside them.
+static bool dec_sigma_ok(double sigma) { return sigma >= 0.5 && sigma <= 2.0; }
+
+// The backward's path: the one-CU kernels' 5-wide gather tables bound the
+// window for sigma >= 1 (<= 4 / sigma + 1 output indices per source texel and
+// axis); below that (up to 9) the generic kernels take the one-CU shapes too.
+static bool dec_bwd_cu(int K, int h, int H, double sigma) { return dec_cu_shape(K, h, H) && sigma >= 1.0; }
+
+// Slab rows (= blocks) of the backward over F frames grouped by grp
 // (0: ungrouped) of which the first `live` per group are processed (0: all).
-int paig_decoder_bwd_blocks(int F, int grp, int live, int K, int h, int H) {
+int paig_decoder_bwd_blocks_sigma(int F, int grp, int live, int K, int h, int H, double sigma) {
   if (F <= 0) return 1;
-  if (dec_cu_shape(K, h, H)) {
+  if (dec_bwd_cu(K, h, H, sigma)) {
     const int NL = dec_live(F, grp, live);
     const int g = NL > 0 ? cdiv(NL, dec_cu_fpb(NL)) : 1;
     return g < 1 ? 1 : g;
@@ -2077,25 +2116,32 @@ int paig_decoder_bwd_blocks(int F, int grp, int live, int K, int h, int H) {
   return g;
 }
 
+int paig_decoder_bwd_blocks(int F, int grp, int live, int K, int h, int H) {
+  return paig_decoder_bwd_blocks_sigma(F, grp, live, K, h, H, 1.0);
+}
+
 size_t paig_decoder_slab_len(int K, int h, int H) { return (size_t)K * h * h * 4 + 3 * (size_t)H * H; }
 
 // Global scratch (floats) needed when the per-frame pixel-gradient image does
 // not fit LDS; 0 when it does.
-size_t paig_decoder_bwd_scratch(int F, int K, int h, int H) {
-  if (dec_cu_shape(K, h, H)) return 0;
+size_t paig_decoder_bwd_scratch_sigma(int F, int K, int h, int H, double sigma) {
+  if (dec_bwd_cu(K, h, H, sigma)) return 0;
   size_t lds = ((size_t)K * h * h * 4 + (size_t)K * 4 * H * H) * 4;
   if (lds <= 120 * 1024) return 0;
-  return (size_t)paig_decoder_bwd_blocks(F, 0, 0, K, h, H) * K * 4 * H * H;
+  return (size_t)paig_decoder_bwd_blocks_sigma(F, 0, 0, K, h, H, sigma) * K * 4 * H * H;
 }
+
+size_t paig_decoder_bwd_scratch(int F, int K, int h, int H) { return paig_decoder_bwd_scratch_sigma(F, K, h, H, 1.0); }
 
 }  // extern "C"
 
 static int dec_fwd(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
                    const float* cont, const float* bg, float* out, long long out_fs, TView t, float* sse, int F, int K,
-                   int h, int H, void* stream) {
+                   int h, int H, double sigma, void* stream) {
+  PAIG_REQUIRE(dec_sigma_ok(sigma), "decoder: sigma=%g outside [0.5, 2]", sigma);
   if (F <= 0) return 0;
   PAIG_REQUIRE(H == 2 * h, "decoder: H=%d must be 2*tmpl=%d", H, 2 * h);
-  PosView pv{pos, pos_outer, pos_inner, pos_grp};
+  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma};
   Src S{tmpl, cont, bg};
   FViewW o{out, out_fs};
   hipStream_t st = (hipStream_t)stream;
@@ -2108,7 +2154,8 @@ static int dec_fwd(const float* pos, long long pos_outer, long long pos_inner, i
 static int dec_bwd(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
                    const float* cont, const float* bg, TView t, WSrc dsse, const float* dout,
                    long long dout_fs, float* dpos, float* slab, float* scratch, int F, int live, int K, int h, int H,
-                   void* stream) {
+                   double sigma, void* stream) {
+  PAIG_REQUIRE(dec_sigma_ok(sigma), "decoder_bwd: sigma=%g outside [0.5, 2]", sigma);
   if (F <= 0) return 0;
   PAIG_REQUIRE(dsse.mode >= 0 && dsse.mode <= 2 && (dsse.mode == 0 || (dsse.B > 0 && dsse.Te > 0 && dsse.R > 0)),
                "decoder_bwd: loss-weight mode %d", dsse.mode);
@@ -2123,14 +2170,14 @@ static int dec_bwd(const float* pos, long long pos_outer, long long pos_inner, i
   // generic ones walk them (zero contribution), so both give the same result
   PAIG_REQUIRE(live == 0 || dout == nullptr, "decoder_bwd: live=%d with a dense dL/dout (dead frames would be skipped)",
                live);
-  PosView pv{pos, pos_outer, pos_inner, pos_grp};
+  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma};
   Src S{tmpl, cont, bg};
   FView d{dout, dout_fs, 0, 0};
   hipStream_t st = (hipStream_t)stream;
-  if (dec_cu_shape(K, h, H)) {
+  if (dec_bwd_cu(K, h, H, sigma)) {
     const int NL = dec_live(F, pos_grp, live);
     const int fpb = dec_cu_fpb(NL > 0 ? NL : 1);
-    const int g = paig_decoder_bwd_blocks(F, pos_grp, live, K, h, H);
+    const int g = paig_decoder_bwd_blocks_sigma(F, pos_grp, live, K, h, H, sigma);
     const int rl = dec_live(F, pos_grp, live) == F ? 0 : live;
     auto launch = [&](auto t8, auto lw) {
       constexpr bool T8 = decltype(t8)::value, LW = decltype(lw)::value;
@@ -2155,22 +2202,37 @@ static int dec_bwd(const float* pos, long long pos_outer, long long pos_inner, i
     PAIG_CHECK_LAUNCH();
     return 0;
   }
-  PAIG_REQUIRE(!t.p8, "decoder_bwd: byte targets need the one-CU kernels (K=%d H=%d)", K, H);
-  PAIG_REQUIRE(dsse.mode == 0, "decoder_bwd: in-kernel loss weights need the one-CU kernels (K=%d H=%d)", K, H);
-  const FView tf{t.p, t.fs, t.gs, t.grp};
-  // generic kernels: every frame is walked (dead ones skipped by their zero weight)
-  const int g = paig_decoder_bwd_blocks(F, 0, 0, K, h, H);
-  const bool need_scratch = paig_decoder_bwd_scratch(F, K, h, H) > 0;
+  // byte targets and in-kernel loss weights: the one-CU shapes (at sigma < 1
+  // through the generic kernels)
+  PAIG_REQUIRE(!t.p8 || dec_cu_shape(K, h, H), "decoder_bwd: byte targets need the one-CU kernels (K=%d H=%d)", K, H);
+  PAIG_REQUIRE(dsse.mode == 0 || dec_cu_shape(K, h, H),
+               "decoder_bwd: in-kernel loss weights need the one-CU kernels (K=%d H=%d)", K, H);
+  // generic kernels: every frame is walked (dead ones skipped by their step or zero weight)
+  const int g = paig_decoder_bwd_blocks_sigma(F, 0, 0, K, h, H, sigma);
+  const bool need_scratch = paig_decoder_bwd_scratch_sigma(F, K, h, H, sigma) > 0;
   PAIG_REQUIRE(!need_scratch || scratch, "decoder_bwd: scratch required");
   const int lds = (K * h * h * 4 + (need_scratch ? 0 : K * 4 * H * H)) * 4;
   float* gs = need_scratch ? scratch : nullptr;
-  if (K == 2)
-    hipLaunchKernelGGL((dec_bwd_k<2>), dim3(g), dim3(256), lds, st, pv, S, tf, dsse.a, d, dpos, slab, gs, F, h, H);
-  else if (K == 3)
-    hipLaunchKernelGGL((dec_bwd_k<3>), dim3(g), dim3(256), lds, st, pv, S, tf, dsse.a, d, dpos, slab, gs, F, h, H);
-  else {
+  if (K != 2 && K != 3) {
     paig_set_error("decoder: unsupported n_objs %d", K);
     return PAIG_E_UNSUPPORTED;
+  }
+  auto launch = [&](auto t8, auto lw) {
+    constexpr bool T8 = decltype(t8)::value, LW = decltype(lw)::value;
+    auto go = [&](auto kern) {
+      if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      hipLaunchKernelGGL(kern, dim3(g), dim3(256), lds, st, pv, S, t, dsse, d, dpos, slab, gs, F, live, h, H);
+    };
+    if (K == 2) go(dec_bwd_k<2, T8, LW>);
+    else go(dec_bwd_k<3, T8, LW>);
+  };
+  const bool t8 = t.p8 && dsse.on();
+  if (dsse.mode != 0) {
+    if (t8) launch(std::true_type{}, std::true_type{});
+    else launch(std::false_type{}, std::true_type{});
+  } else {
+    if (t8) launch(std::true_type{}, std::false_type{});
+    else launch(std::false_type{}, std::false_type{});
   }
   PAIG_CHECK_LAUNCH();
   return 0;
@@ -2178,31 +2240,44 @@ static int dec_bwd(const float* pos, long long pos_outer, long long pos_inner, i
 
 extern "C" {
 
+// The *_sigma entry points take the attention-window scale sigma =
+// np.exp(np.log(log_sig)) of physics_models.py:160-162 (theta0 = theta4 =
+// sigma in fp64, theta2 / theta5 scaled by fl32(sigma) in fp32, :163-167), in
+// [0.5, 2]; the entry points without it mean sigma = 1.
+int paig_decoder_fwd_sigma(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
+                           const float* cont, const float* bg, float* out, long long out_fs, const float* tgt,
+                           long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H,
+                           double sigma, void* stream) {
+  return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
+                 TView{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, sigma, stream);
+}
+
 int paig_decoder_fwd(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
                      const float* cont, const float* bg, float* out, long long out_fs, const float* tgt,
                      long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H,
                      void* stream) {
-  return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
-                 TView{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, stream);
+  return paig_decoder_fwd_sigma(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs, tgt, tgt_fs, tgt_grp,
+                                tgt_gs, sse, F, K, h, H, 1.0, stream);
 }
 
 // The rollout (paig_rollout_fwd's arguments) and the reconstruction decode
 // (paig_decoder_fwd's, fp32 targets and an SSE output) in one launch, where
 // the one-CU decoder serves the shape: (K, H) in {(2, 32), (3, 36), (2, 64)}
 // with 16-byte aligned frames; the cell / D pairs of paig_rollout_fwd.
-int paig_decoder_fwd_rollout(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
-                             const double* p0, const double* p1, float* pvs, int B, int D, int R, const float* pos,
-                             long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
-                             const float* cont, const float* bg, float* out, long long out_fs, const float* tgt,
-                             long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H,
-                             void* stream) {
+int paig_decoder_fwd_rollout_sigma(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
+                                   const double* p0, const double* p1, float* pvs, int B, int D, int R,
+                                   const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                                   const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
+                                   const float* tgt, long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F,
+                                   int K, int h, int H, double sigma, void* stream) {
+  PAIG_REQUIRE(dec_sigma_ok(sigma), "decoder_fwd_rollout: sigma=%g outside [0.5, 2]", sigma);
   PAIG_REQUIRE(B > 0 && F > 0 && R > 0, "decoder_fwd_rollout: B=%d F=%d R=%d", B, F, R);
   PAIG_REQUIRE(cell == 1 || (p0 && p1), "decoder_fwd_rollout: physics params required");
   PAIG_REQUIRE(H == 2 * h && sse && tgt, "decoder_fwd_rollout: H=%d tmpl=%d, targets and an SSE output required", H, h);
   const bool al = ((uintptr_t)out | (uintptr_t)bg | (uintptr_t)tgt) % 16 == 0 && out_fs % 4 == 0 && tgt_fs % 4 == 0 &&
                   tgt_gs % 4 == 0;
   PAIG_REQUIRE(al, "decoder_fwd_rollout: 16-byte aligned frames required");
-  PosView pv{pos, pos_outer, pos_inner, pos_grp};
+  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma};
   Src S{tmpl, cont, bg};
   FViewW o{out, out_fs};
   TView t{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp};
@@ -2234,14 +2309,33 @@ int paig_decoder_fwd_rollout(int cell, const float* pos0, long long pos0_ld, con
   return 0;
 }
 
+int paig_decoder_fwd_rollout(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
+                             const double* p0, const double* p1, float* pvs, int B, int D, int R, const float* pos,
+                             long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
+                             const float* cont, const float* bg, float* out, long long out_fs, const float* tgt,
+                             long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H,
+                             void* stream) {
+  return paig_decoder_fwd_rollout_sigma(cell, pos0, pos0_ld, vel0, dt, p0, p1, pvs, B, D, R, pos, pos_outer, pos_inner,
+                                        pos_grp, tmpl, cont, bg, out, out_fs, tgt, tgt_fs, tgt_grp, tgt_gs, sse, F, K, h,
+                                        H, 1.0, stream);
+}
+
+int paig_decoder_fwd_t8_sigma(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                              const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
+                              const unsigned char* tgt, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
+                              long long tgt_gs, float* sse, int F, int K, int h, int H, double sigma, void* stream) {
+  PAIG_REQUIRE(tgt && sse, "decoder_fwd_t8: byte targets and an SSE output are required");
+  PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_fwd_t8: a row index needs grouped targets");
+  return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
+                 TView{nullptr, tgt, tgt_idx, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, sigma, stream);
+}
+
 int paig_decoder_fwd_t8(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
                         const float* cont, const float* bg, float* out, long long out_fs, const unsigned char* tgt,
                         const long long* tgt_idx, long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H,
                         void* stream) {
-  PAIG_REQUIRE(tgt && sse, "decoder_fwd_t8: byte targets and an SSE output are required");
-  PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_fwd_t8: a row index needs grouped targets");
-  return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
-                 TView{nullptr, tgt, tgt_idx, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, stream);
+  return paig_decoder_fwd_t8_sigma(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs, tgt, tgt_idx, tgt_fs,
+                                   tgt_grp, tgt_gs, sse, F, K, h, H, 1.0, stream);
 }
 
 int paig_decoder_bwd(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
@@ -2250,7 +2344,7 @@ int paig_decoder_bwd(const float* pos, long long pos_outer, long long pos_inner,
                      float* slab, float* scratch, int F, int live, int K, int h, int H, void* stream) {
   return dec_bwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, TView{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp},
                  WSrc{dsse, nullptr, nullptr, nullptr, 0.f, 0, 0, 0, 0, 0}, dout, dout_fs, dpos, slab, scratch, F, live, K, h,
-                 H, stream);
+                 H, 1.0, stream);
 }
 
 int paig_decoder_bwd_t8(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
@@ -2262,7 +2356,7 @@ int paig_decoder_bwd_t8(const float* pos, long long pos_outer, long long pos_inn
   PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_bwd_t8: a row index needs grouped targets");
   return dec_bwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, TView{nullptr, tgt, tgt_idx, tgt_fs, tgt_gs, tgt_grp},
                  WSrc{dsse, nullptr, nullptr, nullptr, 0.f, 0, 0, 0, 0, 0}, dout, dout_fs, dpos, slab, scratch, F, live, K, h,
-                 H, stream);
+                 H, 1.0, stream);
 }
 
 // The backward with either target form (tgt fp32, or tgt8 + tgt_idx bytes:
@@ -2270,12 +2364,14 @@ int paig_decoder_bwd_t8(const float* pos, long long pos_outer, long long pos_inn
 // formed in-kernel from the loss adjoints dt / de / dr (lw_mode 1:
 // reconstruction frames, 2: rollout frames; paig_loss_bwd's values, so no
 // weight arrays and no paig_loss_bwd launch).  lw_mode != 0: the one-CU shapes.
-int paig_decoder_bwd_ex(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
-                        const float* cont, const float* bg, const float* tgt, const unsigned char* tgt8,
-                        const long long* tgt_idx, long long tgt_fs, int tgt_grp, long long tgt_gs, const float* dsse,
-                        int lw_mode, const float* dt, const float* de, const float* dr, float ae, int lB, int lTe,
-                        int lR, int lpred, const float* dout, long long dout_fs, float* dpos, float* slab,
-                        float* scratch, int F, int live, int K, int h, int H, void* stream) {
+// Slab rows / scratch: paig_decoder_bwd_blocks_sigma / _bwd_scratch_sigma.
+int paig_decoder_bwd_ex_sigma(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                              const float* tmpl, const float* cont, const float* bg, const float* tgt,
+                              const unsigned char* tgt8, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
+                              long long tgt_gs, const float* dsse, int lw_mode, const float* dt, const float* de,
+                              const float* dr, float ae, int lB, int lTe, int lR, int lpred, const float* dout,
+                              long long dout_fs, float* dpos, float* slab, float* scratch, int F, int live, int K,
+                              int h, int H, double sigma, void* stream) {
   PAIG_REQUIRE(!tgt != !tgt8, "decoder_bwd_ex: exactly one of the fp32 / byte targets");
   PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_bwd_ex: a row index needs grouped targets");
   PAIG_REQUIRE(lw_mode != 0 || !dt, "decoder_bwd_ex: loss adjoints given with lw_mode 0");
@@ -2283,7 +2379,18 @@ int paig_decoder_bwd_ex(const float* pos, long long pos_outer, long long pos_inn
                lR);
   return dec_bwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, TView{tgt, tgt8, tgt8 ? tgt_idx : nullptr, tgt_fs, tgt_gs, tgt_grp},
                  WSrc{lw_mode ? nullptr : dsse, dt, de, dr, ae, lB, lTe, lR, lpred, lw_mode}, dout, dout_fs, dpos, slab,
-                 scratch, F, live, K, h, H, stream);
+                 scratch, F, live, K, h, H, sigma, stream);
+}
+
+int paig_decoder_bwd_ex(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
+                        const float* cont, const float* bg, const float* tgt, const unsigned char* tgt8,
+                        const long long* tgt_idx, long long tgt_fs, int tgt_grp, long long tgt_gs, const float* dsse,
+                        int lw_mode, const float* dt, const float* de, const float* dr, float ae, int lB, int lTe,
+                        int lR, int lpred, const float* dout, long long dout_fs, float* dpos, float* slab,
+                        float* scratch, int F, int live, int K, int h, int H, void* stream) {
+  return paig_decoder_bwd_ex_sigma(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, tgt, tgt8, tgt_idx, tgt_fs, tgt_grp,
+                                   tgt_gs, dsse, lw_mode, dt, de, dr, ae, lB, lTe, lR, lpred, dout, dout_fs, dpos, slab,
+                                   scratch, F, live, K, h, H, 1.0, stream);
 }
 
 }  // extern "C"
@@ -2313,11 +2420,13 @@ static int stn_bwd(const float* U, const T* theta, const float* dout, float* dU,
 
 extern "C" {
 
-int paig_decoder_parts(const float* pos, long long pos_inner, const float* tmpl, const float* cont, const float* bg,
-                       float* contents, float* masks, int F, int K, int h, int H, void* stream) {
+int paig_decoder_parts_sigma(const float* pos, long long pos_inner, const float* tmpl, const float* cont,
+                             const float* bg, float* contents, float* masks, int F, int K, int h, int H, double sigma,
+                             void* stream) {
+  PAIG_REQUIRE(dec_sigma_ok(sigma), "decoder_parts: sigma=%g outside [0.5, 2]", sigma);
   if (F <= 0) return 0;
   PAIG_REQUIRE(H == 2 * h && H <= MAXH, "decoder_parts: H=%d must be 2*tmpl=%d (<= %d)", H, 2 * h, MAXH);
-  PosView pv{pos, 0, pos_inner, 0};
+  PosView pv{pos, 0, pos_inner, 0, sigma, (float)sigma};
   Src S{tmpl, cont, bg};
   hipStream_t st = (hipStream_t)stream;
   const int g = F < 2048 ? F : 2048;
@@ -2330,6 +2439,11 @@ int paig_decoder_parts(const float* pos, long long pos_inner, const float* tmpl,
   }
   PAIG_CHECK_LAUNCH();
   return 0;
+}
+
+int paig_decoder_parts(const float* pos, long long pos_inner, const float* tmpl, const float* cont, const float* bg,
+                       float* contents, float* masks, int F, int K, int h, int H, void* stream) {
+  return paig_decoder_parts_sigma(pos, pos_inner, tmpl, cont, bg, contents, masks, F, K, h, H, 1.0, stream);
 }
 
 int paig_stn_fwd(const float* U, const float* theta, float* out, int N, int C, int Hi, int Wi, int Ho, int Wo,

@@ -263,6 +263,7 @@ class StepState:
     need_saved: bool = True     # new_state: a backward may follow; _unet_forward (else the inference workspace)
     sw: Switches = None         # new_state: the forward's A/B switches; every stage
     x_view: tuple = None        # new_state: the encoder's frames (pointer, stride, group, group stride)
+    sigma: float = 1.0          # forward: the decoders' window scale (model.decoder_sigma()); forward, backward
     tb: int = 0                 # forward: 1 = the rollout targets are dataset bytes; backward
     tgt_roll: tuple = None      # forward: the rollout decoders' target view; backward
     src: dict = None            # forward: VFN buffers {name: (hidden, raw, post-sigmoid or None)}; backward
@@ -313,6 +314,7 @@ class Engine:
         self.L = lib()
         self.probe = None
         self.last_masked_objs = None
+        self.last_sigma = 1.0           # the last forward's decoder window scale (StepState.sigma)
         self.last_loss_handoff = None   # the last forward's loss-weight hand-off (physics_models._LossHandoff)
         # called once per backward when the early gradient bucket is final
         # (FlatParams.allreduce_early by default; bench.py splits its HIP graph here)
@@ -480,7 +482,9 @@ class Engine:
         lay = Layout(model, B, T, read_switches())
         L = self.L
         x = x.contiguous()
+        sigma = model.decoder_sigma()   # log_sig is read at every forward, as in the reference
         S = self.new_state(lay, x, need_saved)
+        S.sigma = self.last_sigma = sigma
         dev, ws, sw = S.dev, S.ws, S.sw
         st = stream_handle(dev)
         K, F, HW, H, h, D = lay.K, lay.F, lay.HW, lay.H, lay.h, lay.D
@@ -521,7 +525,7 @@ class Engine:
         roll = self._rollout_args(S)
         vel_act = (ptr(S.Xv), ptr(S.v1), ptr(S.v2), ptr(S.vel0))
         dec = (ptr(enc_pos), 0, 2 * K, 0, ptr(tmpl), ptr(cont), ptr(bgp), ptr(recons), lay.frame, *S.x_view,
-               ptr(sse_rec), F, K, h, H)
+               ptr(sse_rec), F, K, h, H, S.sigma)
         # velocity MLP + VFN sources in one launch (independent); then the
         # rollout and the reconstruction decode in one launch
         fuse_vfn = S.vel0 is not None and not lay.alt_vel and sw.fuse_vfn
@@ -541,17 +545,17 @@ class Engine:
         # reconstruction decode (all B*Te frames, SSE vs input fused)
         with self._p("dec_fwd:recon+rollout" if merge_roll else "dec_fwd:recon", 0, self._dec_bytes(F, lay)):
             if merge_roll:
-                L.paig_decoder_fwd_rollout(*roll, *dec, st)
+                L.paig_decoder_fwd_rollout_sigma(*roll, *dec, st)
             else:
-                L.paig_decoder_fwd(*dec, st)
+                L.paig_decoder_fwd_sigma(*dec, st)
 
         # ---- rollout decode (all B*R frames in one launch, SSE vs input[:, ins:])
         out = _empty(B * lay.R * lay.frame, dev)
         sse_roll = _empty(B * lay.R, dev)
-        dec_fwd = L.paig_decoder_fwd_t8 if S.tb else L.paig_decoder_fwd
+        dec_fwd = L.paig_decoder_fwd_t8_sigma if S.tb else L.paig_decoder_fwd_sigma
         with self._p("dec_fwd:rollout", 0, self._dec_bytes(B * lay.R, lay, S.tb or 4)):
             dec_fwd(ptr(S.pvs) + 2 * D * 4, (lay.R + 1) * 2 * D, 2 * D, lay.R, ptr(tmpl), ptr(cont), ptr(bgp),
-                    ptr(out), lay.frame, *S.tgt_roll, ptr(sse_roll), B * lay.R, K, h, H, st)
+                    ptr(out), lay.frame, *S.tgt_roll, ptr(sse_roll), B * lay.R, K, h, H, S.sigma, st)
 
         masks, objs = S.masks, S.objs
         res = {
@@ -761,7 +765,7 @@ class Engine:
 
     # -- backward --------------------------------------------------------
     def _decoder_bwd(self, S, pos, po, pi, pg, tgt, dsse, lw, dout, dpos, slab_p, scr, nfr, live, st):
-        """paig_decoder_bwd_ex over nfr frames at positions (pos, po, pi, pg):
+        """paig_decoder_bwd_ex_sigma (the forward's sigma) over nfr frames at positions (pos, po, pi, pg):
         fp32 (4-tuple) or byte (5-tuple) targets tgt; lw: in-kernel loss
         weights (mode, LossAdjoints) or None (dsse read)."""
         lay = S.lay
@@ -773,9 +777,10 @@ class Engine:
             dsse = None
         else:
             lwa = (0, None, None, None, 0.0, 0, 0, 0, 0)
-        self.L.paig_decoder_bwd_ex(pos, po, pi, pg, ptr(S.src["var_net_template"][1]), ptr(S.src["var_net_content"][1]),
-                                   ptr(S.src["var_net_background"][2]), tf, t8, ti, fs, grp, gs, ptr(dsse), *lwa,
-                                   ptr(dout), lay.frame, dpos, slab_p, scr, nfr, live, lay.K, lay.h, lay.H, st)
+        self.L.paig_decoder_bwd_ex_sigma(pos, po, pi, pg, ptr(S.src["var_net_template"][1]),
+                                         ptr(S.src["var_net_content"][1]), ptr(S.src["var_net_background"][2]), tf, t8,
+                                         ti, fs, grp, gs, ptr(dsse), *lwa, ptr(dout), lay.frame, dpos, slab_p, scr, nfr,
+                                         live, lay.K, lay.h, lay.H, S.sigma, st)
 
     def backward(self, S, d_sse_rec=None, d_sse_roll=None, d_out=None, d_recons=None, d_enc_pos=None, d_pvs=None,
                  roll_live=0, lossw=None):
@@ -806,10 +811,11 @@ class Engine:
         # ---- buffers of the whole decoder / rollout / velocity backward
         slab_len = int(L.paig_decoder_slab_len(K, h, H))
         roll_live = roll_live if (d_out is None and 0 < roll_live < R) else 0
-        nb_rec = L.paig_decoder_bwd_blocks(F, 0, 0, K, h, H)
-        nb_roll = L.paig_decoder_bwd_blocks(B * R, R, roll_live, K, h, H)
+        nb_rec = L.paig_decoder_bwd_blocks_sigma(F, 0, 0, K, h, H, S.sigma)
+        nb_roll = L.paig_decoder_bwd_blocks_sigma(B * R, R, roll_live, K, h, H, S.sigma)
         slab = _empty((nb_rec + nb_roll) * slab_len, dev)
-        scr_n = max(L.paig_decoder_bwd_scratch(F, K, h, H), L.paig_decoder_bwd_scratch(B * R, K, h, H))
+        scr_n = max(L.paig_decoder_bwd_scratch_sigma(F, K, h, H, S.sigma),
+                    L.paig_decoder_bwd_scratch_sigma(B * R, K, h, H, S.sigma))
         scratch = _empty(scr_n, dev) if scr_n else None
         denc = _empty(F * D, dev)   # d enc_pos [B][Te][D]
         dpos_roll = _empty(B * R * D, dev)

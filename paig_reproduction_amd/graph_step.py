@@ -27,6 +27,7 @@ class GraphStep:
         self.eng = model._native()
         self.one = None
         self.graph = None
+        self.sigma = None   # the decoder window scale the graph was captured with (a kernel argument)
         self.replays = 0
 
     def body(self, x):
@@ -50,6 +51,7 @@ class GraphStep:
         if not self.use_graph:
             return
         m, eng = self.m, self.eng
+        self.sigma = m.decoder_sigma()
         if self.one is None:   # the seed gradient must exist before any capture
             self.one = torch.ones((), device=self.xbuf.device)
         torch.cuda.synchronize()
@@ -88,6 +90,9 @@ class GraphStep:
     def __call__(self):
         if self.graph is None:
             return self.eager()
+        if self.m.decoder_sigma() != self.sigma:   # log_sig changed since the capture: capture again
+            self.graph = None
+            self.capture()
         gs, lg = self.graph
         self.replays += 1
         gs[0].replay()

@@ -274,16 +274,18 @@ class _STDecoder(torch.autograd.Function):
         K, H = model.n_objs, model.conv_input_shape[1]
         h = H // 2
         N = pos.shape[0]
+        sigma = model.decoder_sigma()   # this call's: the backward uses its own forward's value
         srcs = model._decoder_sources(dev, st)
         out = torch.empty(N, 3, H, H, device=dev)
-        L.paig_decoder_fwd(ptr(pos), 0, 2 * K, 0, ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"]), ptr(out),
-                           3 * H * H, None, 0, 0, 0, None, N, K, h, H, st)
-        ctx.model, ctx.pos, ctx.srcs = model, pos, srcs
+        L.paig_decoder_fwd_sigma(ptr(pos), 0, 2 * K, 0, ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"]), ptr(out),
+                                 3 * H * H, None, 0, 0, 0, None, N, K, h, H, sigma, st)
+        ctx.model, ctx.pos, ctx.srcs, ctx.sigma = model, pos, srcs, sigma
+        object.__setattr__(model, "_last_decoder_sigma", sigma)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        model, pos, srcs = ctx.model, ctx.pos, ctx.srcs
+        model, pos, srcs, sigma = ctx.model, ctx.pos, ctx.srcs, ctx.sigma
         dev = pos.device
         st = stream_handle(dev)
         L = lib()
@@ -292,16 +294,16 @@ class _STDecoder(torch.autograd.Function):
         N = pos.shape[0]
         dout = dout.float().contiguous()
         slab_len = int(L.paig_decoder_slab_len(K, h, H))
-        nb = L.paig_decoder_bwd_blocks(N, 0, 0, K, h, H)
+        nb = L.paig_decoder_bwd_blocks_sigma(N, 0, 0, K, h, H, sigma)
         slab = torch.empty(nb * slab_len, device=dev)
-        scr_n = L.paig_decoder_bwd_scratch(N, K, h, H)
+        scr_n = L.paig_decoder_bwd_scratch_sigma(N, K, h, H, sigma)
         scratch = torch.empty(scr_n, device=dev) if scr_n else None
         dpos = torch.empty(N, 2 * K, device=dev)
         # no target frames: the SSE weight is null and dL/dout comes dense
         # (the target pointer must still address N valid frames; dout does)
-        L.paig_decoder_bwd(ptr(pos), 0, 2 * K, 0, ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"]), ptr(dout),
-                           3 * H * H, 0, 0, None, ptr(dout), 3 * H * H, ptr(dpos), ptr(slab), ptr(scratch), N, 0, K, h, H,
-                           st)
+        L.paig_decoder_bwd_ex_sigma(ptr(pos), 0, 2 * K, 0, ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"]),
+                                    ptr(dout), None, None, 3 * H * H, 0, 0, None, 0, None, None, None, 0.0, 0, 0, 0, 0,
+                                    ptr(dout), 3 * H * H, ptr(dpos), ptr(slab), ptr(scratch), N, 0, K, h, H, sigma, st)
         dsrc = torch.empty(slab_len, device=dev)
         L.paig_slab_reduce(ptr(slab), nb, slab_len, slab_len, ptr(dsrc), 0, st)
         model._decoder_sources_backward(srcs, dsrc, st)

@@ -252,7 +252,8 @@ class PhysicsNet(BaseNetTorch):
                  input_size=36 * 36,
                  encoder_type="",
                  decoder_type="conv_st_decoder",
-                 device=torch.device("cpu")):
+                 device=torch.device("cpu"),
+                 sigma=1.0):
         super().__init__()
         self.device = device
         assert task in COORD_UNITS
@@ -290,9 +291,10 @@ class PhysicsNet(BaseNetTorch):
         self.extra_valid_fns.append((self.visualize_sequence, [], {}))
         self.extra_test_fns.append((self.visualize_sequence, [], {}))
         tmpl_size = self.conv_input_shape[1] // 2
-        self.log_sig = 1.
-        if self.log_sig != 1.:
-            raise NotImplementedError("sigma != 1")
+        # physics_models.py:155-161: "This parameter can be played with" -- a
+        # plain attribute (no parameter, not in the state_dict), read at every
+        # forward (decoder_sigma)
+        self.log_sig = sigma
         # Network subcomponents (creation order = reference order, for init parity)
         self.var_net_content = VariableFromNetwork([self.n_objs, self.conv_ch, tmpl_size, tmpl_size])
         self.var_net_background = VariableFromNetwork([1, *self.input_shape])
@@ -385,6 +387,19 @@ class PhysicsNet(BaseNetTorch):
         self._flat.ensure()
         self.optimizer = OPTIMIZERS[optimizer](self, self.lr)
 
+    SIGMA_RANGE = (0.5, 2.0)
+
+    def decoder_sigma(self):
+        """The decoders' attention-window scale of this forward, as the
+        reference forms it (physics_models.py:160): np.exp(np.log(log_sig)), a
+        float64.  The HIP decoders serve [0.5, 2]."""
+        with np.errstate(all="ignore"):
+            sigma = float(np.exp(np.log(np.float64(self.log_sig))))
+        lo, hi = self.SIGMA_RANGE
+        if not lo <= sigma <= hi:
+            raise ValueError(f"log_sig={self.log_sig!r}: the decoders support sigma in [{lo}, {hi}]")
+        return sigma
+
     def conv_st_decoder(self, inp):
         """Decode positions [N, coord_units/2] -> frames [N, C, H, W]
         (physics_models.py:151-199): the three VariableFromNetwork sources and
@@ -401,7 +416,7 @@ class PhysicsNet(BaseNetTorch):
         self.template = srcs["tmpl"].view(K, 1, h, h)
         self.contents = srcs["cont"].view(K, 3, h, h)
         self.background_content = srcs["bg"].view(1, 3, H, H)
-        object.__setattr__(self, "_parts", (inp.detach().float().contiguous(), 2 * K, srcs))
+        object.__setattr__(self, "_parts", (inp.detach().float().contiguous(), 2 * K, srcs, self._last_decoder_sigma))
         return out
 
     def check_numerics(self):
@@ -489,14 +504,14 @@ class PhysicsNet(BaseNetTorch):
         cached = getattr(self, "_parts_cache", None)
         if cached is not None and cached[0] is self._parts:
             return cached[1]
-        pos, inner, srcs = self._parts
+        pos, inner, srcs, sigma = self._parts
         K, H = self.n_objs, self.conv_input_shape[1]
         N = pos.shape[0]
         dev = pos.device
         cont = torch.empty(K + 1, N, 3, H, H, device=dev)
         masks = torch.empty(K + 1, N, 3, H, H, device=dev)
-        lib().paig_decoder_parts(ptr(pos), inner, ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"]), ptr(cont),
-                                 ptr(masks), N, K, H // 2, H, stream_handle(dev))
+        lib().paig_decoder_parts_sigma(ptr(pos), inner, ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"]),
+                                       ptr(cont), ptr(masks), N, K, H // 2, H, sigma, stream_handle(dev))
         res = ([cont[k] for k in range(K + 1)], tuple(masks[k] for k in range(K + 1)))
         object.__setattr__(self, "_parts_cache", (self._parts, res))
         return res
@@ -534,7 +549,8 @@ class PhysicsNet(BaseNetTorch):
         # the reference's last decoder call decodes the last rollout step
         R, D = self.pred_steps + self.extrap_steps, self.coord_units // 2
         object.__setattr__(self, "_parts", (pvs.detach()[:, R, :D], (R + 1) * 2 * D,
-                                            {"tmpl": tmpl.detach(), "cont": cont.detach(), "bg": bg.detach()}))
+                                            {"tmpl": tmpl.detach(), "cont": cont.detach(), "bg": bg.detach()},
+                                            eng.last_sigma))
         self._fwd_output = out
         return out
 

@@ -102,6 +102,8 @@ def build_parser():
                    help="1: dataset resident in HBM as uint8, batches gathered on the GPU (F2); 0: host iterators")
     p.add_argument("--synthetic_device", type=int, choices=(0, 1), default=0,
                    help="1: render a missing --synthetic dataset on the GPU and keep it there (no npz written)")
+    p.add_argument("--sigma", type=float, default=1.0,
+                   help="decoder attention-window scale (PhysicsNet.log_sig), in [0.5, 2]: 2 halves the window")
     return p
 
 
@@ -164,7 +166,7 @@ def main(argv=None):
             torch.manual_seed(args.seed)
         net = Model(args.task, args.recurrent_units, args.lstm_layers, cell_type, sl, input_steps, pred_steps,
                     args.autoencoder_loss, args.alt_vel, args.color, input_size, args.encoder_type,
-                    args.decoder_type, device=device)
+                    args.decoder_type, device=device, sigma=args.sigma)
         net.loss_mode = args.loss_mode
         net.conv_math = args.conv_math or ("bf16" if args.dtype == "bf16" else "split")
         net.to(net.device)

@@ -2,7 +2,11 @@
 BASELINE configs' shapes (HIP events around back-to-back launches on one
 stream), with the algorithmic bytes of each launch (engine._dec_bwd_bytes).
 
-usage: python tools/dec_bench.py [reps=50] [cases=all|name,name]
+usage: python tools/dec_bench.py [reps=50] [cases=all|name,name] [--sigma S]
+
+--sigma S (in [0.5, 2]): the *_sigma entry points at that attention-window
+scale, each launch between its own pair of HIP events, the median reported
+(the decoder backward of sigma < 1 takes the generic kernels: DESIGN 4).
 """
 import os
 import sys
@@ -23,8 +27,14 @@ CASES = {
 
 
 def main():
-    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
-    want = sys.argv[2].split(",") if len(sys.argv) > 2 and sys.argv[2] != "all" else list(CASES)
+    argv = list(sys.argv)
+    sigma = None
+    if "--sigma" in argv:
+        i = argv.index("--sigma")
+        sigma = float(argv[i + 1])
+        del argv[i:i + 2]
+    reps = int(argv[1]) if len(argv) > 1 else 50
+    want = argv[2].split(",") if len(argv) > 2 and argv[2] != "all" else list(CASES)
     L = lib()
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
@@ -51,11 +61,24 @@ def main():
             pv = (pos.data_ptr(), 0, 2 * K, 0)
             tv = (x.data_ptr(), fr, 0, 0)
         slab_len = int(L.paig_decoder_slab_len(K, h, H))
-        nb = L.paig_decoder_bwd_blocks(F, R, live, K, h, H)
+        if sigma is None:
+            nb, scr = L.paig_decoder_bwd_blocks(F, R, live, K, h, H), L.paig_decoder_bwd_scratch(F, K, h, H)
+        else:
+            nb = L.paig_decoder_bwd_blocks_sigma(F, R, live, K, h, H, sigma)
+            scr = L.paig_decoder_bwd_scratch_sigma(F, K, h, H, sigma)
         slab = torch.empty(nb * slab_len, device=dev)
-        scr = L.paig_decoder_bwd_scratch(F, K, h, H)
         scratch = torch.empty(scr, device=dev) if scr else None
         dpos = torch.empty(F * 2 * K, device=dev)
+
+        def fwd_s():
+            L.paig_decoder_fwd_sigma(*pv, tmpl.data_ptr(), cont.data_ptr(), bg.data_ptr(), out.data_ptr(), fr, *tv,
+                                     sse.data_ptr(), F, K, h, H, sigma, st)
+
+        def bwd_s():
+            L.paig_decoder_bwd_ex_sigma(*pv, tmpl.data_ptr(), cont.data_ptr(), bg.data_ptr(), tv[0], None, None, *tv[1:],
+                                        w.data_ptr(), 0, None, None, None, 0.0, 0, 0, 0, 0, None, fr, dpos.data_ptr(),
+                                        slab.data_ptr(), None if scratch is None else scratch.data_ptr(), F,
+                                        live if R else 0, K, h, H, sigma, st)
 
         def fwd():
             L.paig_decoder_fwd(*pv, tmpl.data_ptr(), cont.data_ptr(), bg.data_ptr(), out.data_ptr(), fr, *tv,
@@ -69,11 +92,22 @@ def main():
             assert rc == 0, L.paig_last_error()
 
         nlive = B * live if R else F
-        for kind, fn, nbytes in (("fwd", fwd, 2 * F * fr * 4),
-                                 ("bwd", bwd, nlive * fr * 4 + F * 2 * K * 4 + slab_len * 4)):
+        for kind, fn, nbytes in (("fwd", fwd if sigma is None else fwd_s, 2 * F * fr * 4),
+                                 ("bwd", bwd if sigma is None else bwd_s, nlive * fr * 4 + F * 2 * K * 4 + slab_len * 4)):
             for _ in range(3):
                 fn()
             torch.cuda.synchronize()
+            if sigma is not None:
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+                for a, b in ev:
+                    a.record()
+                    fn()
+                    b.record()
+                torch.cuda.synchronize()
+                us = sorted(a.elapsed_time(b) for a, b in ev)[reps // 2] * 1e3
+                print(f"{name:15s} {kind} sigma={sigma:g} frames={F:6d} live={nlive:6d} median {us:9.2f} us "
+                      f"slab_rows={nb}", flush=True)
+                continue
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(reps):
