@@ -31,7 +31,7 @@ extern "C" {
 /* Version of this interface: bumped whenever an entry point's argument list
  * or a data layout it exchanges changes (the Python binding refuses a library
  * of another version). */
-#define PAIG_ABI_VERSION 10
+#define PAIG_ABI_VERSION 11
 const char* paig_last_error(void);
 int paig_abi_version(void);
 /* f16 range guard of the split-precision path.  Activations and gradients
@@ -695,6 +695,64 @@ int paig_adam_f64(double* p, const double* g, double* m, double* v, long long n,
                   double eps, double bc1, double bc2sqrt, void* stream);
 int paig_sgd_f32(float* p, const float* g, float* buf, long long n, float lr, float mom, int first, void* stream);
 int paig_sgd_f64(double* p, const double* g, double* buf, long long n, double lr, double mom, int first, void* stream);
+
+/* ---- gradient norms over the flat gradient buffers, and clipped updates ----
+ * (no reference counterpart: torch.nn.utils.clip_grad_norm_ walks p.grad in
+ * Python; the original PAIG code trained the physics scalars with a learning
+ * rate of their own, physics_models.py:145).
+ *
+ * seg: device table of nseg parameter segments, PAIG_GN_COLS long longs each:
+ *   offset (elements into g32 or g64, any alignment), length (>= 0), kind (32
+ *   or 64), group (0..PAIG_GN_GROUPS-1, or -1 for none) and chunk0, the index
+ *   of the segment's first chunk: segment i owns ceil(length /
+ *   paig_grad_norm_chunk()) consecutive chunks from chunk0, and chunk0 is the
+ *   running sum of those counts in table order.  nchunks is their total.
+ * mask (nullable): one byte per segment; 0 = the segment contributes 0 and its
+ *   slot is never read.
+ * stats: PAIG_GN_SQ0 + nseg doubles:
+ *   [PAIG_GN_NORM]      sqrt of the sum of sq[i] in index order
+ *   [PAIG_GN_COEF]      min(1, max_norm / (norm + 1e-6)) (clip_grad_norm_'s
+ *                       rule, NaN propagating); 1 when max_norm <= 0
+ *   [PAIG_GN_NONFINITE] set to 1 when the norm is inf or NaN; never cleared
+ *                       by the library (the caller zeroes it)
+ *   [PAIG_GN_TOTAL_SQ]  the sum of sq[i]
+ *   [PAIG_GN_GROUP0+g]  sqrt of the sum of sq[i] over the segments of group g
+ *   [PAIG_GN_SQ0+i]     sq[i], the sum of squares of segment i (fp64
+ *                       accumulation of exact products)
+ * Deterministic: chunk c is always reduced by block c in a fixed order, and a
+ * second one-block launch adds the partial sums in a fixed order (no atomics).
+ * scratch: paig_grad_norm_scratch(nchunks) bytes.  A segment outside its
+ * buffer or a chunk outside scratch gives sq[i] = NaN; nothing is read out of
+ * bounds. */
+#define PAIG_GN_COLS 5
+#define PAIG_GN_GROUPS 8
+#define PAIG_GN_NORM 0
+#define PAIG_GN_COEF 1
+#define PAIG_GN_NONFINITE 2
+#define PAIG_GN_TOTAL_SQ 3
+#define PAIG_GN_GROUP0 4
+#define PAIG_GN_SQ0 12
+#define PAIG_GN_MAX_SEGMENTS 4096
+int paig_grad_norm_chunk(void);
+size_t paig_grad_norm_scratch(long long nchunks);
+int paig_grad_norm(const float* g32, long long n32, const double* g64, long long n64, const long long* seg, int nseg,
+                   long long nchunks, const unsigned char* mask, double max_norm, double* stats, void* scratch,
+                   size_t scratch_bytes, void* stream);
+/* the updates above with the gradient multiplied by *coef in registers
+ * ((float)*coef for fp32 elements), coef = &stats[PAIG_GN_COEF]; the gradient
+ * buffers are not written.  paig_rmsprop_mixed_clip takes the fp64 buffer's
+ * learning rate separately. */
+int paig_rmsprop_mixed_clip(float* p32, const float* g32, float* s32, long long n32, double* p64, const double* g64,
+                            double* s64, long long n64, double lr, double lr64, double alpha, double eps,
+                            const double* coef, void* stream);
+int paig_adam_f32_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2,
+                       float eps, float bc1, float bc2sqrt, const double* coef, void* stream);
+int paig_adam_f64_clip(double* p, const double* g, double* m, double* v, long long n, double lr, double b1, double b2,
+                       double eps, double bc1, double bc2sqrt, const double* coef, void* stream);
+int paig_sgd_f32_clip(float* p, const float* g, float* buf, long long n, float lr, float mom, int first,
+                      const double* coef, void* stream);
+int paig_sgd_f64_clip(double* p, const double* g, double* buf, long long n, double lr, double mom, int first,
+                      const double* coef, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ XMAX_SLOTS = 2048
 
 AB_PATH = os.environ.get("PAIG_AB_LIB")
 # include/paig_hip.h PAIG_ABI_VERSION: the SIGNATURES below are this version's
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -154,7 +154,19 @@ SIGNATURES = {
     "paig_adam_f64": (I, [P, P, P, P, LL, F64, F64, F64, F64, F64, F64, P]),
     "paig_sgd_f32": (I, [P, P, P, LL, F32, F32, I, P]),
     "paig_sgd_f64": (I, [P, P, P, LL, F64, F64, I, P]),
+    "paig_grad_norm_chunk": (I, []),
+    "paig_grad_norm_scratch": (SZ, [LL]),
+    "paig_grad_norm": (I, [P, LL, P, LL, P, I, LL, P, F64, P, P, SZ, P]),
+    "paig_rmsprop_mixed_clip": (I, [P, P, P, LL, P, P, P, LL, F64, F64, F64, F64, P, P]),
+    "paig_adam_f32_clip": (I, [P, P, P, P, LL, F32, F32, F32, F32, F32, F32, P, P]),
+    "paig_adam_f64_clip": (I, [P, P, P, P, LL, F64, F64, F64, F64, F64, F64, P, P]),
+    "paig_sgd_f32_clip": (I, [P, P, P, LL, F32, F32, I, P, P]),
+    "paig_sgd_f64_clip": (I, [P, P, P, LL, F64, F64, I, P, P]),
 }
+
+# layout of paig_grad_norm's record and segment table (include/paig_hip.h PAIG_GN_*)
+GN_COLS, GN_GROUPS = 5, 8
+GN_NORM, GN_COEF, GN_NONFINITE, GN_TOTAL_SQ, GN_GROUP0, GN_SQ0 = 0, 1, 2, 3, 4, 12
 
 _QUERY = {"paig_last_error", "paig_abi_version", "paig_f16_range_status", "paig_conv2d_mfma_supported",
           "paig_debug_fwd_block_cap",
@@ -164,7 +176,8 @@ _QUERY = {"paig_last_error", "paig_abi_version", "paig_f16_range_status", "paig_
           "paig_unet_buffer", "paig_unet_query", "paig_localiser_workspace",
           "paig_velmlp_rollout_bwd_workspace",
           "paig_vfn_bwd_blocks", "paig_rollout_bwd_blocks", "paig_decoder_bwd_blocks", "paig_decoder_slab_len",
-          "paig_decoder_bwd_scratch", "paig_decoder_bwd_blocks_sigma", "paig_decoder_bwd_scratch_sigma"}
+          "paig_decoder_bwd_scratch", "paig_decoder_bwd_blocks_sigma", "paig_decoder_bwd_scratch_sigma",
+          "paig_grad_norm_chunk", "paig_grad_norm_scratch"}
 
 
 class PaigError(RuntimeError):

@@ -248,6 +248,212 @@ static inline int grid_for(long long n) {
   return (int)g;
 }
 
+// ------------------------------------------- gradient norms and clipping ---
+// Squared norms of the flat gradients per parameter segment (include/paig_hip.h).
+// Two launches: grad_sq_partial_k, one block per chunk of GN_CHUNK elements of
+// one segment (chunk c is always block c: no result depends on scheduling),
+// then grad_norm_final_k, one block that adds each segment's partial sums in a
+// fixed order and forms the record.  The kernel boundary is the hand-off: a
+// last-block-done epilogue would save one launch but needs a counter zeroed by
+// a memset node per call and an agent-scope acquire in front of the partials.
+constexpr int GN_CHUNK = 4096;   // elements per block: 4 x 16 bytes per thread of fp32
+constexpr int GN_FINAL_WAVES = 16;
+
+struct GnSeg {
+  long long off, len, kind, group, chunk0;
+};
+__device__ __forceinline__ GnSeg gn_seg(const long long* __restrict__ seg, int i) {
+  const long long* s = seg + (long long)i * PAIG_GN_COLS;
+  return GnSeg{s[0], s[1], s[2], s[3], s[4]};
+}
+// the segment lies inside its buffer
+__device__ __forceinline__ bool gn_valid(const GnSeg& s, long long n32, long long n64) {
+  const long long n = s.kind == 64 ? n64 : n32;
+  return (s.kind == 32 || s.kind == 64) && s.off >= 0 && s.len >= 0 && s.off <= n && s.len <= n - s.off;
+}
+__device__ __forceinline__ double sq_acc(float v, double acc) { return fma((double)v, (double)v, acc); }
+
+__global__ void __launch_bounds__(256) grad_sq_partial_k(const float* __restrict__ g32, long long n32,
+                                                         const double* __restrict__ g64, long long n64,
+                                                         const long long* __restrict__ seg, int nseg,
+                                                         const unsigned char* __restrict__ mask,
+                                                         double* __restrict__ part) {
+  __shared__ double red[4];
+  const int c = blockIdx.x, tid = threadIdx.x;
+  // the last segment whose first chunk is <= c (segments without chunks share
+  // their successor's chunk0 and are passed over)
+  int lo = 0, hi = nseg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (seg[(long long)mid * PAIG_GN_COLS + 4] <= c) lo = mid;
+    else hi = mid - 1;
+  }
+  const GnSeg s = gn_seg(seg, lo);
+  const long long e0 = ((long long)c - s.chunk0) * GN_CHUNK;
+  if (!gn_valid(s, n32, n64) || e0 < 0 || e0 >= s.len) return;   // an inconsistent table: the final pass gives NaN
+  if (mask && !mask[lo]) return;                                  // never read: the final pass gives 0
+  const int cnt = (int)(s.len - e0 < GN_CHUNK ? s.len - e0 : GN_CHUNK);
+  double acc = 0.0;
+  if (s.kind == 64) {
+    const double* __restrict__ p = g64 + s.off + e0;
+    for (int i = tid; i < cnt; i += 256) acc = fma(p[i], p[i], acc);
+  } else {
+    // scalar head up to the first 16-byte boundary, float4 interior, scalar tail
+    const float* __restrict__ p = g32 + s.off + e0;
+    int head = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
+    if (head > cnt) head = cnt;
+    const int nv = (cnt - head) >> 2;
+    const float4* __restrict__ pv = reinterpret_cast<const float4*>(p + head);
+#pragma unroll 4
+    for (int i = tid; i < nv; i += 256) {
+      const float4 v = pv[i];
+      acc = sq_acc(v.x, acc);
+      acc = sq_acc(v.y, acc);
+      acc = sq_acc(v.z, acc);
+      acc = sq_acc(v.w, acc);
+    }
+    if (tid < head) acc = sq_acc(p[tid], acc);
+    const int t = head + 4 * nv + tid;
+    if (t < cnt) acc = sq_acc(p[t], acc);
+  }
+  acc = wave_sum_d(acc);
+  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) part[c] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ void __launch_bounds__(64 * GN_FINAL_WAVES) grad_norm_final_k(const long long* __restrict__ seg, int nseg,
+                                                                        const unsigned char* __restrict__ mask,
+                                                                        long long n32, long long n64,
+                                                                        const double* __restrict__ part,
+                                                                        long long nchunks, double max_norm,
+                                                                        double* __restrict__ stats) {
+  __shared__ double ssq[PAIG_GN_MAX_SEGMENTS];
+  __shared__ double gsum[PAIG_GN_GROUPS];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  // one wave per segment: lanes stride over its chunks, then a fixed butterfly
+  for (int i = wv; i < nseg; i += GN_FINAL_WAVES) {
+    const GnSeg s = gn_seg(seg, i);
+    double v = 0.0;
+    if (!(mask && !mask[i])) {
+      const long long nch = (s.len + GN_CHUNK - 1) / GN_CHUNK;
+      if (!gn_valid(s, n32, n64) || s.chunk0 < 0 || s.chunk0 > nchunks || nch > nchunks - s.chunk0) {
+        v = nan("");
+      } else {
+        for (long long j = lane; j < nch; j += 64) v += part[s.chunk0 + j];
+        v = wave_sum_d(v);
+      }
+    }
+    if (lane == 0) {
+      ssq[i] = v;
+      stats[PAIG_GN_SQ0 + i] = v;
+    }
+  }
+  if (threadIdx.x < PAIG_GN_GROUPS) gsum[threadIdx.x] = 0.0;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    for (int i = 0; i < nseg; ++i) {   // index order
+      const double v = ssq[i];
+      tot += v;
+      const long long g = seg[(long long)i * PAIG_GN_COLS + 3];
+      if (g >= 0 && g < PAIG_GN_GROUPS) gsum[g] += v;
+    }
+    const double norm = sqrt(tot);
+    double coef = 1.0;
+    if (max_norm > 0.0) {
+      const double q = max_norm / (norm + 1e-6);
+      coef = q < 1.0 ? q : (q != q ? q : 1.0);   // torch.clamp(max=1): NaN stays NaN
+    }
+    stats[PAIG_GN_NORM] = norm;
+    stats[PAIG_GN_COEF] = coef;
+    if (!(fabs(norm) <= 1.7976931348623157e308)) stats[PAIG_GN_NONFINITE] = 1.0;   // sticky: never cleared here
+    stats[PAIG_GN_TOTAL_SQ] = tot;
+    for (int g = 0; g < PAIG_GN_GROUPS; ++g) stats[PAIG_GN_GROUP0 + g] = sqrt(gsum[g]);
+  }
+}
+
+// The optimizer kernels above with the gradient scaled by the clip coefficient
+// read from the device (the norm record's field), in registers: the gradient
+// buffers keep the unclipped values.  The scaling is one rounded multiply
+// (__fmul_rn / __dmul_rn: never contracted into the update's FMAs), so with
+// coef == 1 every update is the unclipped kernel's, bit for bit.
+__global__ void rmsprop_mixed_clip_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sa,
+                                     long long n, float lr, float alpha, float eps, double* __restrict__ pd,
+                                     const double* __restrict__ gd, double* __restrict__ sd, long long nd, double lrd,
+                                     double alphad, double epsd, int vec, const double* __restrict__ coef) {
+  const double cd = *coef;
+  const float c = (float)cd;
+  if (blockIdx.x == 0)
+    for (long long i = threadIdx.x; i < nd; i += blockDim.x) {
+      const double gi = __dmul_rn(gd[i], cd);
+      double s = sd[i] * alphad;
+      s = s + (1.0 - alphad) * gi * gi;
+      sd[i] = s;
+      pd[i] = pd[i] - lrd * gi / (sqrt(s) + epsd);
+    }
+  auto upd = [&](float pi, float graw, float si, float& po, float& so) __attribute__((always_inline)) {
+    const float gi = __fmul_rn(graw, c);
+    float s = si * alpha;
+    s = s + (1.f - alpha) * gi * gi;
+    so = s;
+    po = pi - lr * gi / (sqrtf(s) + eps);
+  };
+  if (vec) {
+    const int n4 = (int)(n / 4);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
+      const float4 gv = reinterpret_cast<const float4*>(g)[i];
+      const float4 sv = reinterpret_cast<const float4*>(sa)[i];
+      const float4 pv = reinterpret_cast<const float4*>(p)[i];
+      float4 po, so;
+      upd(pv.x, gv.x, sv.x, po.x, so.x);
+      upd(pv.y, gv.y, sv.y, po.y, so.y);
+      upd(pv.z, gv.z, sv.z, po.z, so.z);
+      upd(pv.w, gv.w, sv.w, po.w, so.w);
+      reinterpret_cast<float4*>(sa)[i] = so;
+      reinterpret_cast<float4*>(p)[i] = po;
+    }
+    const long long t = 4ll * n4 + blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (t < n) upd(p[t], g[t], sa[t], p[t], sa[t]);
+    return;
+  }
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    upd(p[i], g[i], sa[i], p[i], sa[i]);
+}
+
+__device__ __forceinline__ float clip_mul(float g, double c) { return __fmul_rn(g, (float)c); }
+__device__ __forceinline__ double clip_mul(double g, double c) { return __dmul_rn(g, c); }
+
+template <typename T>
+__global__ void adam_clip_k(T* __restrict__ p, const T* __restrict__ g, T* __restrict__ m, T* __restrict__ v,
+                            long long n, T lr, T b1, T b2, T eps, T bc1, T bc2sqrt, const double* __restrict__ coef) {
+  const double c = *coef;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const T gi = clip_mul(g[i], c);
+    const T mi = m[i] * b1 + (T(1) - b1) * gi;
+    const T vi = v[i] * b2 + (T(1) - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    const T denom = sqrt(vi) / bc2sqrt + eps;
+    p[i] = p[i] - (lr / bc1) * mi / denom;
+  }
+}
+
+template <typename T>
+__global__ void sgd_clip_k(T* __restrict__ p, const T* __restrict__ g, T* __restrict__ buf, long long n, T lr, T mom,
+                           int first, const double* __restrict__ coef) {
+  const double c = *coef;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    T d = clip_mul(g[i], c);
+    if (buf) {
+      const T b = first ? d : buf[i] * mom + d;
+      buf[i] = b;
+      d = b;
+    }
+    p[i] = p[i] - lr * d;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -418,6 +624,85 @@ int paig_sgd_f32(float* p, const float* g, float* buf, long long n, float lr, fl
 int paig_sgd_f64(double* p, const double* g, double* buf, long long n, double lr, double mom, int first, void* stream) {
   if (n <= 0) return 0;
   hipLaunchKernelGGL(sgd_k<double>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, lr, mom, first);
+  PAIG_CHECK_LAUNCH();
+  return 0;
+}
+
+int paig_grad_norm_chunk(void) { return GN_CHUNK; }
+
+size_t paig_grad_norm_scratch(long long nchunks) { return sizeof(double) * (size_t)(nchunks > 1 ? nchunks : 1); }
+
+int paig_grad_norm(const float* g32, long long n32, const double* g64, long long n64, const long long* seg, int nseg,
+                   long long nchunks, const unsigned char* mask, double max_norm, double* stats, void* scratch,
+                   size_t scratch_bytes, void* stream) {
+  PAIG_REQUIRE(nseg >= 1 && nseg <= PAIG_GN_MAX_SEGMENTS, "paig_grad_norm: nseg=%d (1..%d)", nseg,
+               PAIG_GN_MAX_SEGMENTS);
+  PAIG_REQUIRE(n32 >= 0 && n64 >= 0 && nchunks >= 0 && nchunks < (1ll << 31), "paig_grad_norm: n32=%lld n64=%lld "
+               "nchunks=%lld", n32, n64, nchunks);
+  PAIG_REQUIRE(seg && stats && (nchunks == 0 || scratch), "paig_grad_norm: null table, record or scratch");
+  PAIG_REQUIRE(scratch_bytes >= paig_grad_norm_scratch(nchunks), "paig_grad_norm: scratch %zu < %zu bytes",
+               scratch_bytes, paig_grad_norm_scratch(nchunks));
+  double* part = (double*)scratch;
+  if (nchunks > 0) {
+    hipLaunchKernelGGL(grad_sq_partial_k, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, g32, n32, g64,
+                       n64, seg, nseg, mask, part);
+    PAIG_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(grad_norm_final_k, dim3(1), dim3(64 * GN_FINAL_WAVES), 0, (hipStream_t)stream, seg, nseg, mask,
+                     n32, n64, part, nchunks, max_norm, stats);
+  PAIG_CHECK_LAUNCH();
+  return 0;
+}
+
+int paig_rmsprop_mixed_clip(float* p32, const float* g32, float* s32, long long n32, double* p64, const double* g64,
+                            double* s64, long long n64, double lr, double lr64, double alpha, double eps,
+                            const double* coef, void* stream) {
+  if (n32 <= 0 && n64 <= 0) return 0;
+  PAIG_REQUIRE(coef, "paig_rmsprop_mixed_clip: null coef");
+  const int vec = n32 < (1ll << 31) && ((uintptr_t)p32 | (uintptr_t)g32 | (uintptr_t)s32) % 16 == 0;
+  const long long nb = n32 > 0 ? (vec ? n32 / 4 + 1 : n32) : 1;
+  hipLaunchKernelGGL(rmsprop_mixed_clip_k, dim3(grid_for(nb)), dim3(256), 0, (hipStream_t)stream, p32, g32, s32, n32,
+                     (float)lr, (float)alpha, (float)eps, p64, g64, s64, n64, lr64, alpha, eps, vec, coef);
+  PAIG_CHECK_LAUNCH();
+  return 0;
+}
+
+int paig_adam_f32_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2,
+                       float eps, float bc1, float bc2sqrt, const double* coef, void* stream) {
+  if (n <= 0) return 0;
+  PAIG_REQUIRE(coef, "paig_adam_f32_clip: null coef");
+  hipLaunchKernelGGL(adam_clip_k<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, b1,
+                     b2, eps, bc1, bc2sqrt, coef);
+  PAIG_CHECK_LAUNCH();
+  return 0;
+}
+
+int paig_adam_f64_clip(double* p, const double* g, double* m, double* v, long long n, double lr, double b1, double b2,
+                       double eps, double bc1, double bc2sqrt, const double* coef, void* stream) {
+  if (n <= 0) return 0;
+  PAIG_REQUIRE(coef, "paig_adam_f64_clip: null coef");
+  hipLaunchKernelGGL(adam_clip_k<double>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, b1,
+                     b2, eps, bc1, bc2sqrt, coef);
+  PAIG_CHECK_LAUNCH();
+  return 0;
+}
+
+int paig_sgd_f32_clip(float* p, const float* g, float* buf, long long n, float lr, float mom, int first,
+                      const double* coef, void* stream) {
+  if (n <= 0) return 0;
+  PAIG_REQUIRE(coef, "paig_sgd_f32_clip: null coef");
+  hipLaunchKernelGGL(sgd_clip_k<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, lr, mom,
+                     first, coef);
+  PAIG_CHECK_LAUNCH();
+  return 0;
+}
+
+int paig_sgd_f64_clip(double* p, const double* g, double* buf, long long n, double lr, double mom, int first,
+                      const double* coef, void* stream) {
+  if (n <= 0) return 0;
+  PAIG_REQUIRE(coef, "paig_sgd_f64_clip: null coef");
+  hipLaunchKernelGGL(sgd_clip_k<double>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, lr, mom,
+                     first, coef);
   PAIG_CHECK_LAUNCH();
   return 0;
 }

@@ -15,7 +15,25 @@ import weakref
 import torch
 import torch.distributed as dist
 
-from ._lib import lib, ptr, stream_handle
+from ._lib import GN_COEF, GN_COLS, GN_GROUP0, GN_GROUPS, GN_NONFINITE, GN_NORM, GN_SQ0, lib, ptr, stream_handle
+
+# the parameter groups of the per-group gradient norms (FlatParams.group_of):
+# their order is the group id of the segment table
+GROUPS = ("unet", "localiser", "velocity", "decoder", "physics")
+_GROUP_PREFIXES = (("encoder.shallow_unet.", "unet"), ("encoder.unet.", "unet"), ("encoder.", "localiser"),
+                   ("velocity_encoder.", "velocity"), ("var_net_", "decoder"), ("rollout_cell.", "physics"))
+assert len(GROUPS) <= GN_GROUPS
+
+
+def segment_table(segs, chunk):
+    """[(kind, offset, length, group id)] -> (int64 [n, GN_COLS] host tensor,
+    number of chunks): paig_grad_norm's segment table (include/paig_hip.h), each
+    segment owning ceil(length / chunk) consecutive chunks in table order."""
+    rows, c0 = [], 0
+    for kind, off, num, grp in segs:
+        rows.append((off, num, kind, grp, c0))
+        c0 += -(-num // chunk)
+    return torch.tensor(rows, dtype=torch.int64).reshape(len(rows), GN_COLS), c0
 
 
 # parameter (by id) -> (FlatParams, name): lets a standalone submodule call
@@ -63,6 +81,27 @@ class FlatParams:
         self._redirect = None
         self._early_work = None
         self.n32_early = 0
+        self._segments = None
+
+    @staticmethod
+    def group_of(name):
+        """The gradient-norm group of a parameter name (one of GROUPS)."""
+        for prefix, grp in _GROUP_PREFIXES:
+            if name.startswith(prefix):
+                return grp
+        raise KeyError(f"{name}: no gradient-norm group")
+
+    def segments(self):
+        """(device segment table, number of chunks, groups present): one row
+        per entry of self.index, in its order, for paig_grad_norm.  Built at
+        the first use after a rebuild()."""
+        if self._segments is None:
+            grp = [self.group_of(n) for n in self.index]
+            table, nchunks = segment_table([(kind, off, num, GROUPS.index(g))
+                                            for (kind, off, num, _), g in zip(self.index.values(), grp)],
+                                           lib().paig_grad_norm_chunk())
+            self._segments = (table.to(self.device), nchunks, tuple(g for g in GROUPS if g in grp))
+        return self._segments
 
     def _params(self):
         pd = dict(self.model.named_parameters())
@@ -120,6 +159,7 @@ class FlatParams:
             self.n32_early += p.numel()
         self.device = dev
         self._early_work = None
+        self._segments = None   # the segment table follows the index
         return True
 
     def _params_by_id(self):
@@ -270,13 +310,30 @@ class FlatOptimizer:
 
     Exposes param_groups/zero_grad/step/state_dict like torch.optim, and
     performs the data-parallel gradient all-reduce before the update when a
-    process group is initialised (the reference is single-GPU)."""
+    process group is initialised (the reference is single-GPU).
 
-    def __init__(self, model, kind, lr, **hp):
+    Off by default (the step is then the same launches as without them):
+      * max_grad_norm > 0: global-norm clipping by torch's clip_grad_norm_
+        rule.  The norm is taken on the device over the flat gradient buffers
+        (paig_grad_norm, after the data-parallel all-reduce, so every rank clips
+        by the same number) and the update kernels read the coefficient from
+        the device and scale the gradient in registers.  Unlike torch's
+        in-place clip, the gradient buffers are NOT rewritten: p.grad after
+        step() holds the unclipped gradient.
+      * physics_lr_mult: the fp64 buffer (rollout_cell.k / .equil / .g) steps
+        with lr * physics_lr_mult.
+      * grad_norms: measure the norms every step (grad_norms(), check_finite())
+        without clipping.
+    All three live in param_groups[0] and travel with state_dict()."""
+
+    def __init__(self, model, kind, lr, max_grad_norm=0.0, physics_lr_mult=1.0, grad_norms=False, **hp):
         self.model = model
         self.kind = kind
-        self.param_groups = [{"params": [p for _, p in model._flat._params()], "lr": lr, **hp}]
+        self.param_groups = [{"params": [p for _, p in model._flat._params()], "lr": lr, **hp,
+                              "max_grad_norm": float(max_grad_norm), "physics_lr_mult": float(physics_lr_mult),
+                              "grad_norms": bool(grad_norms)}]
         self.hp = hp
+        self._gn = None       # (segment table, stats record, chunk scratch, segment mask) of paig_grad_norm
         self.state = {}
         self.steps = 0        # steps taken by every parameter (the fused path)
         self._psteps = None   # per-parameter steps once a step skipped some (grad None), as torch counts them
@@ -293,6 +350,53 @@ class FlatOptimizer:
                 self._bufs = (z32(), z64())
             self.steps = 0
             self._psteps = None
+        g = self.param_groups[0]
+        if (g.get("max_grad_norm", 0.0) > 0 or g.get("grad_norms")) and (self._gn is None or
+                                                                         self._gn[0] is not flat.segments()[0]):
+            table, nchunks, _ = flat.segments()
+            dev = flat.p32.device
+            stats = torch.zeros(GN_SQ0 + table.shape[0], device=dev, dtype=torch.float64)
+            stats[GN_COEF] = 1.0
+            scratch = torch.empty(lib().paig_grad_norm_scratch(nchunks) // 8, device=dev, dtype=torch.float64)
+            self._gn = (table, stats, scratch, torch.ones(table.shape[0], device=dev, dtype=torch.uint8))
+
+    def _grad_norm(self, max_norm, have=None):
+        """Launch paig_grad_norm over the flat gradients (over the parameters
+        flagged in ``have`` only, when given): the record it fills is what
+        grad_norms() and check_finite() read and the clipped updates scale by."""
+        flat = self.model._flat
+        table, stats, scratch, mask = self._gn
+        if have is not None:
+            mask.copy_(torch.tensor(have, dtype=torch.uint8))
+        lib().paig_grad_norm(ptr(flat.g32), flat.n32, ptr(flat.g64) if flat.n64 else None, flat.n64, ptr(table),
+                             table.shape[0], flat.segments()[1], ptr(mask) if have is not None else None,
+                             float(max_norm), ptr(stats), ptr(scratch), scratch.numel() * 8,
+                             stream_handle(flat.p32.device))
+
+    def grad_norms(self):
+        """{"total": norm, group: norm of its parameters' gradients} of the
+        last step, for the groups the model has parameters in: 0-dim float64
+        device tensors (views of the norm record: no kernel, no sync; they show
+        the latest step's values when read)."""
+        if self._gn is None:
+            raise RuntimeError("grad_norms(): no norm has been taken yet (needs max_grad_norm > 0 or "
+                               "grad_norms=True, and a step())")
+        stats = self._gn[1]
+        out = {"total": stats[GN_NORM]}
+        for grp in self.model._flat.segments()[2]:
+            out[grp] = stats[GN_GROUP0 + GROUPS.index(grp)]
+        return out
+
+    def check_finite(self):
+        """Raise FloatingPointError if a gradient norm was inf or NaN since the
+        last call (the record's sticky flag, cleared here).  Synchronises the
+        device: for log steps only."""
+        if self._gn is None:
+            return
+        stats = self._gn[1]
+        if float(stats[GN_NONFINITE].item()) != 0.0:
+            stats[GN_NONFINITE].zero_()
+            raise FloatingPointError("non-finite gradient norm since the last check")
 
     def zero_grad(self, set_to_none=True):
         for _, p in self.model._flat._params():
@@ -309,19 +413,34 @@ class FlatOptimizer:
         flat.allreduce_grads()
         params = flat._params()
         have = [p.grad is not None for _, p in params]
-        if all(have) and self._psteps is None:
+        fused = all(have) and self._psteps is None
+        hyper = self.param_groups[0]
+        clip, mult = float(hyper.get("max_grad_norm", 0.0)), float(hyper.get("physics_lr_mult", 1.0))
+        if clip > 0 or hyper.get("grad_norms"):
+            # after the all-reduce: every data-parallel rank sees the same norm;
+            # on the per-parameter path over the parameters that have a gradient
+            self._grad_norm(clip, None if fused else have)
+        coef = ptr(self._gn[1]) + 8 * GN_COEF if clip > 0 else None
+        if fused:
             # every parameter has a gradient and the same step count: one
             # fused launch per dtype over the whole flat buffers
             self.steps += 1
-            if self.kind == "rmsprop":   # both dtypes in one launch
+            if self.kind == "rmsprop" and coef is None and (mult == 1.0 or not flat.n64):   # both dtypes in one launch
                 a, eps = self.hp.get("alpha", 0.99), self.hp.get("eps", 1e-8)
                 lib().paig_rmsprop_mixed(ptr(flat.p32), ptr(flat.g32), ptr(self._bufs[0]), flat.n32, ptr(flat.p64),
                                          ptr(flat.g64), ptr(self._bufs[1]) if flat.n64 else None, flat.n64,
                                          float(self.param_groups[0]["lr"]), a, eps, stream_handle(flat.p32.device))
                 return None
-            self._launch(32, 0, flat.n32, self.steps)
+            if self.kind == "rmsprop" and coef is not None:   # both dtypes in one launch, each with its lr
+                a, eps = self.hp.get("alpha", 0.99), self.hp.get("eps", 1e-8)
+                lr = float(self.param_groups[0]["lr"])
+                lib().paig_rmsprop_mixed_clip(ptr(flat.p32), ptr(flat.g32), ptr(self._bufs[0]), flat.n32,
+                                              ptr(flat.p64), ptr(flat.g64), ptr(self._bufs[1]) if flat.n64 else None,
+                                              flat.n64, lr, lr * mult, a, eps, coef, stream_handle(flat.p32.device))
+                return None
+            self._launch(32, 0, flat.n32, self.steps, coef)
             if flat.n64:
-                self._launch(64, 0, flat.n64, self.steps)
+                self._launch(64, 0, flat.n64, self.steps, coef)
             return None
         # torch semantics: a parameter whose grad is None is skipped (no
         # update, no state change, no step count)
@@ -331,18 +450,21 @@ class FlatOptimizer:
             if h:
                 self._psteps[n] += 1
                 kind, off, num, _ = flat.index[n]
-                self._launch(kind, off, num, self._psteps[n])
+                self._launch(kind, off, num, self._psteps[n], coef)
         if len(set(self._psteps.values())) == 1:   # back in lockstep: the fused path again
             self.steps = next(iter(self._psteps.values()))
             self._psteps = None
         return None
 
-    def _launch(self, kind, off, num, step):
-        """The update of flat elements [off, off + num) of one dtype."""
+    def _launch(self, kind, off, num, step, coef=None):
+        """The update of flat elements [off, off + num) of one dtype; with
+        ``coef`` (device address of the clip coefficient) by the _clip kernels."""
         flat = self.model._flat
         L = lib()
         st = stream_handle(flat.p32.device)
         lr = float(self.param_groups[0]["lr"])
+        if kind == 64:   # the physics parameters' own learning rate
+            lr = lr * float(self.param_groups[0].get("physics_lr_mult", 1.0))
         e32, e64 = 4 * off, 8 * off
 
         def at(t, e):
@@ -352,7 +474,14 @@ class FlatOptimizer:
             a, eps = self.hp.get("alpha", 0.99), self.hp.get("eps", 1e-8)
             # one launch for both dtypes when called for the whole buffers
             # (fp32 hyper-parameters rounded as torch's fp32 math does)
-            if kind == 32:
+            if coef is not None:
+                if kind == 32:
+                    L.paig_rmsprop_mixed_clip(at(flat.p32, e32), at(flat.g32, e32), at(self._bufs[0], e32), num, None,
+                                              None, None, 0, lr, lr, a, eps, coef, st)
+                else:
+                    L.paig_rmsprop_mixed_clip(None, None, None, 0, at(flat.p64, e64), at(flat.g64, e64),
+                                              at(self._bufs[1], e64), num, lr, lr, a, eps, coef, st)
+            elif kind == 32:
                 L.paig_rmsprop_mixed(at(flat.p32, e32), at(flat.g32, e32), at(self._bufs[0], e32), num, None, None,
                                      None, 0, lr, a, eps, st)
             else:
@@ -363,21 +492,27 @@ class FlatOptimizer:
             eps = self.hp.get("eps", 1e-8)
             bc1 = 1 - b1 ** step
             bc2s = math.sqrt(1 - b2 ** step)
+            tail = (st,) if coef is None else (coef, st)
             if kind == 32:
-                L.paig_adam_f32(at(flat.p32, e32), at(flat.g32, e32), at(self._bufs[0], e32), at(self._bufs[1], e32),
-                                num, lr, b1, b2, eps, bc1, bc2s, st)
+                (L.paig_adam_f32 if coef is None else L.paig_adam_f32_clip)(
+                    at(flat.p32, e32), at(flat.g32, e32), at(self._bufs[0], e32), at(self._bufs[1], e32),
+                    num, lr, b1, b2, eps, bc1, bc2s, *tail)
             else:
-                L.paig_adam_f64(at(flat.p64, e64), at(flat.g64, e64), at(self._bufs[2], e64), at(self._bufs[3], e64),
-                                num, lr, b1, b2, eps, bc1, bc2s, st)
+                (L.paig_adam_f64 if coef is None else L.paig_adam_f64_clip)(
+                    at(flat.p64, e64), at(flat.g64, e64), at(self._bufs[2], e64), at(self._bufs[3], e64),
+                    num, lr, b1, b2, eps, bc1, bc2s, *tail)
         else:  # sgd / momentum
             mom = self.hp.get("momentum", 0.0)
             first = int(step == 1)
+            tail = (st,) if coef is None else (coef, st)
             if kind == 32:
-                L.paig_sgd_f32(at(flat.p32, e32), at(flat.g32, e32), at(self._bufs[0], e32) if mom else None, num, lr,
-                               mom, first, st)
+                (L.paig_sgd_f32 if coef is None else L.paig_sgd_f32_clip)(
+                    at(flat.p32, e32), at(flat.g32, e32), at(self._bufs[0], e32) if mom else None, num, lr,
+                    mom, first, *tail)
             else:
-                L.paig_sgd_f64(at(flat.p64, e64), at(flat.g64, e64), at(self._bufs[1], e64) if mom else None, num, lr,
-                               mom, first, st)
+                (L.paig_sgd_f64 if coef is None else L.paig_sgd_f64_clip)(
+                    at(flat.p64, e64), at(flat.g64, e64), at(self._bufs[1], e64) if mom else None, num, lr,
+                    mom, first, *tail)
 
     def state_dict(self):
         return {"kind": self.kind, "steps": self.steps, "psteps": None if self._psteps is None else dict(self._psteps),

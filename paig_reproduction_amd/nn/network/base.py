@@ -32,10 +32,19 @@ logger = logging.getLogger("torch")
 root_path = os.path.join(os.path.dirname(os.path.realpath(__file__)), "..", "..")
 
 OPTIMIZERS = {
-    "adam": lambda model, lr: FlatOptimizer(model, "adam", lr),
-    "rmsprop": lambda model, lr: FlatOptimizer(model, "rmsprop", lr),
-    "momentum": lambda model, lr: FlatOptimizer(model, "sgd", lr, momentum=0.9),
-    "sgd": lambda model, lr: FlatOptimizer(model, "sgd", lr),
+    "adam": lambda model, lr, **kw: FlatOptimizer(model, "adam", lr, **kw),
+    "rmsprop": lambda model, lr, **kw: FlatOptimizer(model, "rmsprop", lr, **kw),
+    "momentum": lambda model, lr, **kw: FlatOptimizer(model, "sgd", lr, momentum=0.9, **kw),
+    "sgd": lambda model, lr, **kw: FlatOptimizer(model, "sgd", lr, **kw),
+}
+
+# what an exactly-zero gradient norm of a parameter group usually means
+ZERO_GRAD_HINTS = {
+    "unet": "encoder U-Net gradients are exactly zero: dead ReLU head?",
+    "localiser": "encoder localiser gradients are exactly zero: saturated position head?",
+    "velocity": "velocity encoder gradients are exactly zero: no rollout loss reaches it?",
+    "decoder": "decoder (var_net_*) gradients are exactly zero: the loss does not see the decoder?",
+    "physics": "physics parameter gradients are exactly zero: the rollout does not depend on them?",
 }
 
 
@@ -184,9 +193,13 @@ class BaseNetTorch(torch.nn.Module):
                 self.optimizer.step()
                 self.run_extra_fns("train")
                 if step % print_interval == 0:
+                    norms = self._grad_norm_metrics()
                     log_metrics(logger, "train - iter=%s" % step, self.train_metrics)
                     if hasattr(self, "check_numerics"):
                         self.check_numerics()
+                    if norms is not None:
+                        self.optimizer.check_finite()
+                        self._warn_zero_grad_groups(norms)
                 step += 1
 
             if ep % eval_every_n_epochs == 0:
@@ -202,6 +215,27 @@ class BaseNetTorch(torch.nn.Module):
 
         test_metrics_results = self.eval_performance(batch_size, type='test')
         log_metrics(logger, "test - epoch=%s" % epochs, test_metrics_results)
+
+    def _grad_norm_metrics(self):
+        """With the optimizer's gradient norms on: grad_norm and
+        grad_norm/<group> of the step just taken into train_metrics (device
+        values; they are read when the line is logged).  None when off."""
+        if not (self.optimizer.param_groups[0].get("grad_norms") or
+                self.optimizer.param_groups[0].get("max_grad_norm", 0.0) > 0):
+            return None
+        norms = self.optimizer.grad_norms()
+        for k, v in norms.items():
+            self.train_metrics["grad_norm" if k == "total" else "grad_norm/" + k] = v
+        return norms
+
+    def _warn_zero_grad_groups(self, norms):
+        """One warning per parameter group, the first time its gradient norm
+        is exactly 0 at a log step."""
+        seen = self.__dict__.setdefault("_zero_grad_warned", set())
+        for k, v in norms.items():
+            if k != "total" and k not in seen and float(v) == 0.0:
+                seen.add(k)
+                logger.warning(ZERO_GRAD_HINTS[k])
 
     @staticmethod
     def _is_rank0():

@@ -380,12 +380,24 @@ class PhysicsNet(BaseNetTorch):
         eval_losses = [self.pred_loss, self.extrap_loss, self.recons_loss]
         return train_loss, eval_losses
 
-    def build_optimizer(self, base_lr, optimizer="rmsprop", anneal_lr=True):
+    def build_optimizer(self, base_lr, optimizer="rmsprop", anneal_lr=True, max_grad_norm=None, physics_lr_mult=None,
+                        grad_norms=None):
+        """The reference's positional signature (physics_models.py:144-149),
+        plus the flat optimizer's gradient-norm options (FlatOptimizer); None
+        falls back to the environment (PAIG_MAX_GRAD_NORM, PAIG_PHYSICS_LR_MULT,
+        PAIG_GRAD_NORMS), as conv_math does, and from there to off."""
         self.base_lr = base_lr
         self.anneal_lr = anneal_lr
         self.lr = base_lr
         self._flat.ensure()
-        self.optimizer = OPTIMIZERS[optimizer](self, self.lr)
+        if max_grad_norm is None:
+            max_grad_norm = float(os.environ.get("PAIG_MAX_GRAD_NORM", "0"))
+        if physics_lr_mult is None:
+            physics_lr_mult = float(os.environ.get("PAIG_PHYSICS_LR_MULT", "1"))
+        if grad_norms is None:
+            grad_norms = os.environ.get("PAIG_GRAD_NORMS", "0").strip().lower() not in ("", "0", "false", "no")
+        self.optimizer = OPTIMIZERS[optimizer](self, self.lr, max_grad_norm=max_grad_norm,
+                                               physics_lr_mult=physics_lr_mult, grad_norms=grad_norms)
 
     SIGMA_RANGE = (0.5, 2.0)
 

@@ -14,6 +14,12 @@ Additive flags only:
   --seed S                       shared shuffle seed (required for DDP sharding).
   --device_data {1,0}            1 (default): uint8 dataset resident in HBM, each
         batch gathered on the GPU; 0: the reference's host path.
+  --clip_grad_norm X             clip the global gradient norm to X before the update
+        (torch's clip_grad_norm_ rule, taken on the device; 0 = off, the default).
+  --physics_lr_mult M            the physics parameters (rollout_cell.*) step with
+        base_lr * M (default 1).
+  --log_grad_norms               total and per-group gradient norms on the train lines,
+        a warning when a group's gradients are exactly zero.
   --synthetic_device {0,1}       1: with --synthetic N and the task's npz missing,
         render the data on the GPU instead (nn/datasets/synth_device.py: HIP
         integrators + rasteriser) and keep it in HBM; no npz is written.  Same
@@ -104,6 +110,12 @@ def build_parser():
                    help="1: render a missing --synthetic dataset on the GPU and keep it there (no npz written)")
     p.add_argument("--sigma", type=float, default=1.0,
                    help="decoder attention-window scale (PhysicsNet.log_sig), in [0.5, 2]: 2 halves the window")
+    p.add_argument("--clip_grad_norm", type=float, default=0.0,
+                   help="clip the global gradient norm to this value before the update (0: off)")
+    p.add_argument("--physics_lr_mult", type=float, default=1.0,
+                   help="learning rate of the physics parameters (rollout_cell.*), as a multiple of --base_lr")
+    p.add_argument("--log_grad_norms", action="store_true",
+                   help="log the total and per-group gradient norms on the train lines")
     return p
 
 
@@ -175,17 +187,19 @@ def main(argv=None):
                 dist.broadcast(t, 0)
         return net
 
+    optim = {"max_grad_norm": args.clip_grad_norm, "physics_lr_mult": args.physics_lr_mult,
+             "grad_norms": args.log_grad_norms}
     if not args.test_mode:
         network = make(seq_len)
         its = iterators(args, data_file, seq_len, rank, world, device)
         network.get_data(its)
-        network.build_optimizer(args.base_lr, args.optimizer, args.anneal_lr)
+        network.build_optimizer(args.base_lr, args.optimizer, args.anneal_lr, **optim)
         network.initialize_graph(args.save_dir, args.use_ckpt, args.ckpt_dir)
         network.train_model(args.epochs, args.batch_size, args.save_every_n_epochs, args.eval_every_n_epochs,
                             args.print_interval, args.debug)
 
     network = make(test_seq_len)
-    network.build_optimizer(args.base_lr, args.optimizer, args.anneal_lr)
+    network.build_optimizer(args.base_lr, args.optimizer, args.anneal_lr, **optim)
     network.initialize_graph(args.save_dir, True, args.ckpt_dir)
     its = iterators(args, test_data_file, test_seq_len, rank, world, device)
     network.get_data(its)
