@@ -113,7 +113,7 @@ constexpr int sbwd_minw(int CIN, int COUT, int H, int PM, bool PF) {
   if (PM == 2 && CIN == 24 && COUT == 8 && H == 32) return 3;
   if (CIN == 8 && COUT == 8 && H == 36) return PF ? 2 : 3;
   if (CIN == 8 && COUT == 16 && H == 18) return PM == 2 ? 4 : 3;
-  if (CIN == 16 && COUT == 16 && H == 18) return PF ? 2 : 3;
+  if (CIN == 16 && COUT == 16 && H == 18) return PF && PM != 2 ? 2 : 3;
   return 2;
 }
 
@@ -127,6 +127,18 @@ constexpr bool sbwd_auxp(int CIN, int COUT, int H, int PM, bool UPS, bool PF) {
   if (UPS && H == 36) return false;
   if (PM == 0) return !(PF && CIN == 16 && COUT == 16 && H == 16);
   return !((UPS && CIN == 32 && H == 16) || (CIN == 8 && COUT == 16 && H == 16));
+}
+
+// the shapes whose registers cannot hold the hoisted per-unit addressing
+// across the tile loop (measured: -Rpass-analysis=kernel-resource-usage shows
+// a spill, or more registers than the shape's blocks per CU leave): they
+// recompute it per tile
+constexpr bool sbwd_hoist(int CIN, int COUT, int H, int PM, bool PF) {
+  if (PF && PM == 0 && ((CIN == 8 && H == 32) || H == 64)) return false;
+  if (PF && PM == 2 && H == 18) return false;
+  if (CIN == 24 && H == 36 && PM == 0) return false;
+  if (H == 18 && ((CIN == 8 && PM == 2) || (CIN == 16 && COUT == 16 && PM == 0))) return false;
+  return true;
 }
 
 // 4 waves split the weight-gradient N-tiles (each wave owns every 4th one
@@ -189,6 +201,7 @@ struct SBwdCfg {
   static constexpr int XREG = XIMG * 2 * NIMG > UPB ? XIMG * 2 * NIMG : UPB;
   static constexpr int LDS = (IMGD + WIMG) * 2 * NIMG + XREG + (UPS ? UPW * 4 : 0);
   static constexpr bool VEC4 = W % 4 == 0;
+  static constexpr bool HOIST = sbwd_hoist(CIN, COUT, H, PM, PF);
   // X prefetched a tile ahead where its registers are cheap (else loaded
   // when staged)
   static constexpr bool XPIPE = !UPS && NLX * 8 <= 32;
@@ -199,6 +212,9 @@ struct SBwdCfg {
   static constexpr int MINW = MW0 < LDSB ? MW0 : LDSB;
   static_assert(H % RT == 0, "RT divides H");
   static_assert(KS == 3, "3x3 layers (the 1x1 heads are fused elsewhere)");
+  // no channel tails inside a staging unit (a tail channel would need an
+  // out-of-range offset of its own: its plane lies inside the descriptor)
+  static_assert(COUT % 8 == 0 && CIN % 4 == 0, "staging units of 8 dY / 4 X channels");
   static_assert(!UPS || (FPT == 1 && RT % 2 == 0 && W % 2 == 0), "fused upsample: whole even row blocks of one frame");
   // PF: the 2x2 max pool of this layer's output folded into the dY staging
   // (a staging unit's pixel pair is one pooling window's columns)
@@ -417,35 +433,117 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
   constexpr int HP = H / 2, WP = W / 2;
   using UP = UpStage<UPS ? CIN : 1, H, W, FPT, RT>;
   UP up;
+  // ---- addressing that depends on the thread alone, once per block.  Per
+  // staging unit: its byte offset inside the tile's frames less the tile's
+  // row origin (dvo / xvo), its image row less the halo (drow / xrow: frame
+  // row y0 + row; idle lanes get a row that no tile has) and its LDS slot
+  // (dso / xso).  Whole-frame tiles (NRB == 1: y0 = 0) know their halo rows
+  // here: those units' offsets are BUF_OOR from the start.  Per tile there
+  // remain scalar work (the descriptors of the tile's frames) and, on row
+  // tiles, one add and one select per unit
+  auto row_ok = [&](int gy) { return (unsigned)gy < (unsigned)H; };
+  auto d_unit = [&](int i, int& vo, int& row, int& so) {
+    const int xp = UPX * (i % W2), r = (i / W2) % ROWSD, cc = (i / (W2 * ROWSD)) % CCD, fi = i / (W2 * ROWSD * CCD);
+#ifdef PAIG_BWD_NOLOAD   // diagnostic builds only (wrong results): no dY unit is in range
+    const bool in = false;
+#else
+    const bool in = i < NID;
+#endif
+    row = in ? r - PADL - EXT : -(1 << 20);
+    vo = (fi * (int)dy.fs + cc * 8 * (int)HW + (r - PADL - EXT) * W + xp) * 4;
+    if (NRB == 1 && !row_ok(row)) vo = BUF_OOR;
+    so = ((fi * ROWSD + r) * RPD + (xp + PADL) * PSD + cc) * 8;
+  };
+  constexpr int NLH = C::HOIST ? NLD : 1;
+  int dvo[NLH], drow[NLH], dso[NLH];
+  if constexpr (C::HOIST) {
+#pragma unroll
+    for (int l = 0; l < NLD; ++l) d_unit(tid + l * 256, dvo[l], drow[l], dso[l]);
+  }
+  // unit l of this thread (not hoisted: from a thread id the compiler cannot
+  // hoist the arithmetic of)
+  auto d_get = [&](int l, int& vo, int& row, int& so) {
+    if constexpr (C::HOIST) {
+      vo = dvo[l];
+      row = drow[l];
+      so = dso[l];
+    } else {
+      d_unit(opaque(tid) + l * 256, vo, row, so);
+    }
+  };
+  // PF: pooled gradient / window code offsets less the window row.  Two
+  // more registers per unit, which the pool-fold kernels do not have (held
+  // across the tile loop they spill): recomputed per tile there
+  auto pf_unit = [&](int i, int& po, int& co) {
+    const int xp = UPX * (i % W2), cc = (i / (W2 * ROWSD)) % CCD, fi = i / (W2 * ROWSD * CCD);
+    po = (fi * (int)dpool.fs + cc * 8 * (HP * WP) + (xp >> 1)) * 4;
+    co = fi * (int)pcode_fs + (cc * (HP * WP) + (xp >> 1)) * 8;
+  };
+  auto x_unit = [&](int i, int& vo, int& row, int& so) {
+    const int xp = UPX * (i % W2), r = (i / W2) % ROWS, cq = (i / (W2 * ROWS)) % CQ, fi = i / (W2 * ROWS * CQ);
+    row = i < NIX ? r - PADL : -(1 << 20);
+    vo = (fi * (int)x.fs + cq * 4 * (int)XPLANE + (r - PADL) * W + xp) * 4;
+    if (NRB == 1 && !row_ok(row)) vo = BUF_OOR;
+    so = xplane(cq) + ((fi * ROWS + r) * TWX + xp + OFFX) * 4;
+  };
+  constexpr int NXH = C::XPIPE && C::HOIST ? NLX : 1;
+  int xvo[NXH], xrow[NXH], xso[NXH];
+  if constexpr (C::XPIPE && C::HOIST) {
+#pragma unroll
+    for (int l = 0; l < NLX; ++l) x_unit(tid + l * 256, xvo[l], xrow[l], xso[l]);
+  }
+  auto x_get = [&](int l, int& vo, int& row, int& so) {
+    if constexpr (C::HOIST) {
+      vo = xvo[l];
+      row = xrow[l];
+      so = xso[l];
+    } else {
+      x_unit(opaque(tid) + l * 256, vo, row, so);
+    }
+  };
+  int uvo[UPS ? UP::NLS : 1], urow[UPS ? UP::NLS : 1];
+  if constexpr (UPS) {
+#pragma unroll
+    for (int l = 0; l < UP::NLS; ++l) UP::unit(tid + l * 256, (int)x.fs, uvo[l], urow[l]);
+  }
+  // frames of tile t that the views own (0 past the last tile)
+  auto tile_nf = [&](int f0) {
+    const int n = F - f0;
+    return n < FPT ? n : FPT;
+  };
+  // the unit's offset in tile rows y0 ..: the halo rows outside the frame
+  // would land in the neighbouring frame or plane, inside the descriptor
+  auto tile_vo = [&](int vo, int row, int y0) {
+    if constexpr (NRB == 1) return vo;
+    else return row_ok(y0 + row) ? vo + y0 * W * 4 : BUF_OOR;
+  };
   auto load_d = [&](int t) {
-    const int f0 = (t / NRB) * FPT, y0 = (t % NRB) * RT;
-    const float* fb = dy.frame(f0 < F ? f0 : 0);
+    const int f0 = (t / NRB) * FPT, y0 = (t % NRB) * RT, nf = tile_nf(f0);
+    const brsrc rd = tile_rsrc(dy.frame(f0), dy.fs, nf, COUT * (int)HW);
+    brsrc rp, rc;
+    if constexpr (PF) {
+      rp = tile_rsrc(dpool.frame(f0), dpool.fs, nf, COUT * HP * WP);
+      rc = tile_rsrc(pcode + (long long)f0 * pcode_fs, pcode_fs, nf, CCD * HP * WP * 8, 1);
+    }
 #pragma unroll
     for (int l = 0; l < NLD; ++l) {
-      const int i = tid + l * 256;
-      const int xp = UPX * (i % W2), r = (i / W2) % ROWSD, cc = (i / (W2 * ROWSD)) % CCD, fi = i / (W2 * ROWSD * CCD);
-      const int gy = y0 + r - PADL - EXT;
-#ifdef PAIG_BWD_NOLOAD   // diagnostic builds only (wrong results): dY reads from a hot zero buffer
-      const bool ok = false;
-#else
-      const bool ok = i < NID && f0 + fi < F && gy >= 0 && gy < H;
-#endif
-      const int off = fi * (int)dy.fs + cc * 8 * (int)HW + gy * W + xp;
-      static_assert(8 * HW <= 8 * 4096, "paig_zero_planes covers the unit");
-      const float* base = ok ? fb + off : paig_zero_planes;
+      int vo0, row, so;
+      d_get(l, vo0, row, so);
+      const int vo = tile_vo(vo0, row, y0);
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        const float* q = COUT % 8 == 0 || cc * 8 + c < COUT ? base + c * (int)HW : paig_zeros;
-        pd[l][c] = UPX == 2 ? *reinterpret_cast<const float2*>(q) : make_float2(*q, 0.f);
+        pd[l][c] = UPX == 2 ? buf_ld2(rd, vo, c * (int)HW * 4) : make_float2(buf_ld1(rd, vo, c * (int)HW * 4), 0.f);
       }
       if constexpr (PF) {
-        const int pw = (gy >> 1) * WP + (xp >> 1);
-        const float* pb = ok ? dpool.frame(f0) + fi * (int)dpool.fs + cc * 8 * (HP * WP) + pw : paig_zero_planes;
+        const int wr = ((y0 + row) >> 1) * WP;   // the window's row (any parity of y0: 3bp's 9-row tiles)
+        const bool ok = NRB == 1 ? vo != BUF_OOR : row_ok(y0 + row);
+        int po, co;
+        pf_unit(opaque(tid) + l * 256, po, co);
+        const int vp = ok ? po + wr * 4 : BUF_OOR;
 #pragma unroll
-        for (int c = 0; c < 8; ++c) dpv[l][c] = pb[c * (HP * WP)];
-        const unsigned char* cb = ok ? pcode + (long long)(f0 + fi) * pcode_fs + ((long long)cc * HP * WP + pw) * 8
-                                     : reinterpret_cast<const unsigned char*>(paig_zeros);
-        pcv[l] = *reinterpret_cast<const uint2*>(cb);
+        for (int c = 0; c < 8; ++c) dpv[l][c] = buf_ld1(rp, vp, c * (HP * WP) * 4);
+        const u32x2 cv = __builtin_amdgcn_raw_buffer_load_b64(rc, ok ? co + wr * 8 : BUF_OOR, 0, 0);
+        pcv[l] = make_uint2(cv.x, cv.y);
       }
     }
   };
@@ -457,9 +555,9 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
     const int y0 = (t % NRB) * RT;
 #pragma unroll
     for (int l = 0; l < NLD; ++l) {
-      const int i = tid + l * 256;
-      const int r = (i / W2) % ROWSD;
-      const int pr = ((y0 + r - PADL - EXT) & 1) * 2;   // window row of this unit: bits pr, pr + 1
+      int vo, row, so;
+      d_get(l, vo, row, so);
+      const int pr = ((y0 + row) & 1) * 2;   // window row of this unit: bits pr, pr + 1
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const unsigned b = ((c < 4 ? pcv[l].x : pcv[l].y) >> (8 * (c & 3))) & 255u;
@@ -471,32 +569,34 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
       }
     }
   };
-  auto load_x = [&](int t, int i, float2* v) {
-    const int f0 = (t / NRB) * FPT, y0 = (t % NRB) * RT;
-    const int xp = UPX * (i % W2), r = (i / W2) % ROWS, cq = (i / (W2 * ROWS)) % CQ, fi = i / (W2 * ROWS * CQ);
-    const int gy = y0 + r - PADL;
-    const bool ok = i < NIX && f0 + fi < F && gy >= 0 && gy < H;
-    const float* fb = x.frame(f0 < F ? f0 : 0);
-    const int off = fi * (int)x.fs + cq * 4 * (int)XPLANE + gy * W + xp;
-    const float* base = ok ? fb + off : paig_zero_planes;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float* q = CIN % 4 == 0 || cq * 4 + c < CIN ? base + c * (int)XPLANE : paig_zeros;
-      v[c] = UPX == 2 ? *reinterpret_cast<const float2*>(q) : make_float2(*q, 0.f);
-    }
+  // the X frames of tile t (UPS: the half-resolution source)
+  auto x_rsrc = [&](int t) {
+    const int f0 = (t / NRB) * FPT;
+    return tile_rsrc(x.frame(f0), x.fs, tile_nf(f0), CIN * (int)XPLANE);
   };
+  auto load_x = [&](brsrc rx, int t, int vo0, int row, float2* v) {
+    const int vo = tile_vo(vo0, row, (t % NRB) * RT);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      v[c] = UPX == 2 ? buf_ld2(rx, vo, c * (int)XPLANE * 4) : make_float2(buf_ld1(rx, vo, c * (int)XPLANE * 4), 0.f);
+  };
+  // (t == ntiles, after a block's last tile: nothing to prefetch)
   auto issue = [&](int t) {
+    if (t >= ntiles) return;
     load_d(t);
     if constexpr (UPS) {
-      up.issue(x, F, (t / NRB) * FPT, (t % NRB) * RT, tid);
+      up.issue(x_rsrc(t), (t % NRB) * RT, uvo, urow);
     } else if constexpr (C::XPIPE) {
+      const brsrc rx = x_rsrc(t);
 #pragma unroll
-      for (int l = 0; l < NLX; ++l) load_x(t, tid + l * 256, px[l]);
+      for (int l = 0; l < NLX; ++l) {
+        int vo, row, so;
+        x_get(l, vo, row, so);
+        load_x(rx, t, vo, row, px[l]);
+      }
     }
   };
-  auto put_d = [&](int i, const float2* v) {
-    const int xp = UPX * (i % W2), r = (i / W2) % ROWSD, cc = (i / (W2 * ROWSD)) % CCD, fi = i / (W2 * ROWSD * CCD);
-    const int o = ((fi * ROWSD + r) * RPD + (xp + PADL) * PSD + cc) * 8;
+  auto put_d = [&](int o, const float2* v) {   // o: the unit's LDS slot (dso)
     s16x8 h0, l0, h1, l1;
     if constexpr (PM == 0) {
       pf32x2 sv[8];
@@ -532,9 +632,7 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
       if (PM != 2) *reinterpret_cast<s16x8*>(Dl + o + PSD * 8) = l1;
     }
   };
-  auto put_x = [&](int i, const float2* v) {
-    const int xp = UPX * (i % W2), r = (i / W2) % ROWS, cq = (i / (W2 * ROWS)) % CQ, fi = i / (W2 * ROWS * CQ);
-    const int o = xplane(cq) + ((fi * ROWS + r) * TWX + xp + OFFX) * 4;
+  auto put_x_at = [&](int o, const float2* v) {   // o: the unit's LDS slot (xso)
     s16x8 hv, lv;
     if constexpr (PM == 0) {
       pf32x2 sv[4];
@@ -569,6 +667,10 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
       *reinterpret_cast<s16x4*>(Xh + o) = s16x4{hv[0], hv[1], hv[2], hv[3]};
       if (PM != 2) *reinterpret_cast<s16x4*>(Xl + o) = s16x4{lv[0], lv[1], lv[2], lv[3]};
     }
+  };
+  auto put_x = [&](int i, const float2* v) {   // unit i (the staging loops that walk the units)
+    const int xp = UPX * (i % W2), r = (i / W2) % ROWS, cq = (i / (W2 * ROWS)) % CQ, fi = i / (W2 * ROWS * CQ);
+    put_x_at(xplane(cq) + ((fi * ROWS + r) * TWX + xp + OFFX) * 4, v);
   };
   // this wave's max |dY| of the prefetched tile into smax[wv] (before the
   // loop-top barrier; the commit after it reads the block max)
@@ -610,10 +712,13 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
     for (int l = 0; l < NLD; ++l) {
       const int i = tid + l * 256;
       if (NID % 256 != 0 && i >= NID) break;
-      put_d(i, pd[l]);
-      // bias partials: the tile's own rows (not the halo), frames < F
-      const int r = (i / W2) % ROWSD, fi = i / (W2 * ROWSD * CCD);
-      if (r >= PADL + EXT && r < PADL + EXT + RT && f0 + fi < F) {
+      int vo, row, so;
+      d_get(l, vo, row, so);
+      put_d(so, pd[l]);
+      // bias partials: the tile's own rows (not the halo).  Frames >= F add
+      // the zeros their loads returned (+0 each: a partial that is -0 ends
+      // as +0 either way, in the slab sums that start from +0)
+      if ((unsigned)row < (unsigned)RT) {
 #pragma unroll
         for (int c = 0; c < 8; ++c) bacc[l][c] += pd[l][c].x + pd[l][c].y;
       }
@@ -710,20 +815,45 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
       for (int l = 0; l < NLX; ++l) {
         const int i = tid + l * 256;
         if (NIX % 256 != 0 && i >= NIX) break;
-        put_x(i, px[l]);
+        int vo, row, so;
+        x_get(l, vo, row, so);
+        put_x_at(so, px[l]);
       }
     } else {
+      const brsrc rx = x_rsrc(t);
 #pragma unroll 1
       for (int i = tid; i < NIX; i += 256) {
         float2 v[4];
-        load_x(t, i, v);
-        put_x(i, v);
+        int vo, row, so;
+        x_unit(i, vo, row, so);
+        load_x(rx, t, vo, row, v);
+        put_x_at(so, v);
       }
     }
   };
 
+  // AUXP: this lane's ReLU'-mask offsets inside the tile's frames, less the
+  // row origin (and, plain layers, less the 16-channel tile); lanes without
+  // an item are out of range from the start
+  int avo[C::AUXP ? (UPS ? C::NOI : MW) : 1];
+  if constexpr (C::AUXP && UPS) {
+#pragma unroll
+    for (int k = 0; k < C::NOI; ++k) {
+      const int o = tid + 256 * k;
+      const int q = o % C::WQU, sr = (o / C::WQU) % (RT / 2), ci = o / (C::WQU * (RT / 2));
+      avo[k] = o < C::NOU ? ((ci * (H / 2) + sr) * C::WSU + C::IKU * q) * 4 : BUF_OOR;
+    }
+  } else if constexpr (C::AUXP) {
+#pragma unroll
+    for (int mt = 0; mt < MW; ++mt) {
+      const int pix = (wv * MW + mt) * 16 + (lane >> 4) * 4;
+      const int fi = pix / (RT * W), rem = pix % (RT * W);
+      avo[mt] = pix < TPXV ? (fi * (int)aux.fs + (lane & 15) * (int)HW + rem) * 4 : BUF_OOR;
+    }
+  }
+
   int lt = blockIdx.x;
-  auto tile_of = [&](int l) { return l < ntiles ? xcd_tile(l, ntiles) : ntiles; };
+  auto tile_of =[&](int l) { return l < ntiles ? xcd_tile(l, ntiles) : ntiles; };
   issue(tile_of(lt));
   if (PM == 0 && xm.p) {
     // the launch's X exponent: max over the forward's per-block slots
@@ -760,30 +890,24 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
     fIKU auxu[C::AUXP && UPS ? C::NOI : 1];
     if constexpr (C::AUXP) {
       if (flags & 2) {
+        // the mask's frames of this tile; the tile's row origin (and the
+        // 16-channel tile) in the scalar offset
+        const brsrc ra = tile_rsrc(aux.frame(f0), aux.fs, tile_nf(f0), CIN * (int)XPLANE);
         if constexpr (UPS) {
 #pragma unroll
           for (int k = 0; k < C::NOI; ++k) {
-            const int o = tid + 256 * k;
-            const int q = o % C::WQU, sr = (o / C::WQU) % (RT / 2), ci = o / (C::WQU * (RT / 2));
-            const bool ok = o < C::NOU && f0 < F;
-            const float* ap = ok ? aux.frame(f0) + ((long long)ci * (H / 2) + y0 / 2 + sr) * C::WSU + C::IKU * q
-                                 : paig_zero_planes;
-            auxu[k] = *reinterpret_cast<const fIKU*>(ap);
+            const int so = (y0 / 2) * C::WSU * 4;
+            if constexpr (C::IKU == 4) auxu[k] = buf_ld4(ra, avo[k], so);
+            else if constexpr (C::IKU == 2) auxu[k] = __builtin_bit_cast(fIKU, buf_ld2(ra, avo[k], so));
+            else auxu[k] = __builtin_bit_cast(fIKU, buf_ld1(ra, avo[k], so));
           }
         } else {
 #pragma unroll
           for (int nt = 0; nt < NTD; ++nt) {
-            const int ci = nt * 16 + (lane & 15);
+            const bool cok = CIN % 16 == 0 || nt * 16 + (lane & 15) < CIN;
 #pragma unroll
-            for (int mt = 0; mt < MW; ++mt) {
-              const int pix = (wv * MW + mt) * 16 + (lane >> 4) * 4;
-              const int fi = pix / (RT * W), rem = pix % (RT * W);
-              const int f = f0 + fi;
-              const bool ok = ci < CIN && pix < TPXV && f < F;
-              const float* ap = ok ? aux.frame(f) + ci * HW + (long long)(y0 + rem / W) * W + rem % W
-                                   : paig_zero_planes;
-              auxv[mt][nt] = *reinterpret_cast<const f32x4*>(ap);
-            }
+            for (int mt = 0; mt < MW; ++mt)
+              auxv[mt][nt] = buf_ld4(ra, cok ? avo[mt] : BUF_OOR, (nt * 16 * (int)HW + y0 * W) * 4);
           }
         }
       }
@@ -1130,6 +1254,12 @@ static int sbwd_launch(FView x, FView dy, FViewW dx, FView aux, const float* w, 
   PAIG_REQUIRE(!xm.p || (xm.n % 4 == 0 && (reinterpret_cast<uintptr_t>(xm.p) & 15) == 0),
                "conv split bwd: xmax needs 16-byte alignment and a multiple of 4 slots (%d)", xm.n);
   PAIG_REQUIRE(!(flags & 2) || aux.p, "conv split bwd: ReLU' mask (flags & 2) without aux");
+  // the prefetch addresses a tile's frames by 32-bit byte offsets from the
+  // tile's first frame (descriptors rebased per tile: no bound on F)
+  constexpr long long SPAN = (1ll << 31) / (4 * C::FPT) - 8 * 4096;
+  PAIG_REQUIRE(x.fs < SPAN && dy.fs < SPAN && aux.fs < SPAN && dpool.fs < SPAN && pcode_fs < 4 * SPAN &&
+                   x.fs >= 0 && dy.fs >= 0 && aux.fs >= 0 && dpool.fs >= 0 && pcode_fs >= 0,
+               "conv split bwd: a frame stride does not fit the tile's 32-bit byte offsets");
   PAIG_REQUIRE(!PF || (dpool.p && pcode && (reinterpret_cast<uintptr_t>(pcode) & 7) == 0 && pcode_fs % 8 == 0),
                "conv split bwd: pool fold needs the pooled gradient and 8-byte aligned window codes");
   hipLaunchKernelGGL(k, dim3(nb), dim3(256), LDS, st, x, dy, dx, aux, w, flags, slab, F, ntiles, xm,

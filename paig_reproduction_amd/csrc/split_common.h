@@ -84,6 +84,39 @@ __device__ __forceinline__ s16x4 tr_read(const short* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
 }
 
+// Raw buffer loads (the fused backward's prefetch): a descriptor over one
+// tile's frames of an operand view, built from wave-uniform values, and one
+// 32-bit byte offset per lane.  The hardware range check returns 0 for every
+// byte at or past the extent and does not touch memory there, so a unit past
+// the view (frame tails, the prefetch after the last tile: extent 0) needs no
+// address select; a unit that would land INSIDE the extent without being
+// wanted (halo rows above / below a frame, idle lanes, channel tails) is
+// given BUF_OOR, which is past every extent by construction (extents are
+// < 2^31, launch-checked).  s: wave-uniform byte offset (channel plane, row
+// origin), added after the range check of the per-lane offset.
+typedef __amdgpu_buffer_rsrc_t brsrc;
+constexpr int BUF_OOR = (int)0x80000000u;
+__device__ __forceinline__ brsrc buf_rsrc(const void* p, int bytes) {
+  // dword 3: DATA_FORMAT = 32 (gfx9 raw buffers), no swizzle, stride 0
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+// nf frames (0: nothing readable) of frame stride fs, cf floats each, from
+// the tile's first frame
+__device__ __forceinline__ brsrc tile_rsrc(const void* frame0, long long fs, int nf, int cf, int esz = 4) {
+  return buf_rsrc(frame0, nf > 0 ? ((nf - 1) * (int)fs + cf) * esz : 0);
+}
+__device__ __forceinline__ float buf_ld1(brsrc r, int vo, int s) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, s, 0));
+}
+__device__ __forceinline__ float2 buf_ld2(brsrc r, int vo, int s) {
+  // (the whole vector is cast: a cast of one element, v.y, reads element 0)
+  const pf32x2 v = __builtin_bit_cast(pf32x2, __builtin_amdgcn_raw_buffer_load_b64(r, vo, s, 0));
+  return make_float2(v.x, v.y);
+}
+__device__ __forceinline__ f32x4 buf_ld4(brsrc r, int vo, int s) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, vo, s, 0));
+}
+
 // Fused 2x bilinear upsample input (c7, c10: the reference's torchvision
 // Resize feeding a conv, blocks.py:260,269): a tile's half-resolution source
 // window (rows y0/2 - 1 .. y0/2 + RT/2, all columns, fp32) is prefetched a
@@ -120,6 +153,25 @@ struct UpStage {
       const float* src = ok ? x.frame(f0) + fi * (int)x.fs + c * HS * WS + srow * WS + VS * q : paig_zeros;
       if constexpr (VS == 4) v[l] = *reinterpret_cast<const f32x4*>(src);
       else v1[l] = *src;
+    }
+  }
+  // The same prefetch through buffer loads (the fused backward).  unit():
+  // once per block, unit i's byte offset inside the tile's frames less the
+  // row origin (uo) and its window row less one (ur: source row y0/2 + ur;
+  // idle lanes get a row that is never in the frame).  issue(): r spans the
+  // tile's frames (tile_rsrc); rows outside the frame take BUF_OOR
+  static __device__ __forceinline__ void unit(int i, int fs, int& uo, int& ur) {
+    const int q = i % QS, sr = (i / QS) % SRN, c = (i / (QS * SRN)) % CIN, fi = i / (QS * SRN * CIN);
+    ur = i < NSU ? sr - 1 : -(1 << 20);
+    uo = (fi * fs + c * HS * WS + (sr - 1) * WS + VS * q) * 4;
+  }
+  __device__ __forceinline__ void issue(brsrc r, int y0, const int* uo, const int* ur) {
+    const int ro = (y0 / 2) * WS * 4;
+#pragma unroll
+    for (int l = 0; l < NLS; ++l) {
+      const int vo = (unsigned)(y0 / 2 + ur[l]) < (unsigned)HS ? uo[l] + ro : BUF_OOR;
+      if constexpr (VS == 4) v[l] = buf_ld4(r, vo, 0);
+      else v1[l] = buf_ld1(r, vo, 0);
     }
   }
   // max |v| of the prefetched window: a bound on its upsampled values (convex

@@ -24,6 +24,7 @@ LAYERS = {
     "c5": (16, 32, 8, "", 0, 0), "c6": (32, 32, 8, "", 1, 0), "c7": (32, 16, 16, "up", 1, 0),
     "c8": (32, 16, 16, "", 0, 0), "c9": (16, 16, 16, "", 1, 0), "c10": (16, 16, 32, "up", 1, 0),
     "c11": (24, 8, 32, "", 0, 0), "c12": (8, 8, 32, "", 1, 0),
+    "b7": (32, 16, 18, "up", 1, 0), "b10": (16, 16, 36, "up", 1, 0),   # 3bp's c7 / c10 (36 x 36 frames)
     "u2": (16, 16, 64, "pool", 1, 0), "u3": (16, 32, 32, "", 0, 0), "u17": (16, 16, 64, "", 1, 0),
 }
 PHASES = ["setup", "wait+max+bar", "commit-tail", "issue", "wgrad", "dgrad", "epilogue", "slab", "put_d", "ups_win",
