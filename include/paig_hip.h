@@ -611,6 +611,62 @@ int paig_decoder_parts_sigma(const float* pos, long long pos_inner, const float*
                              const float* bg, float* contents, float* masks, int F, int K, int h, int H, double sigma,
                              void* stream);
 
+/* ---- the learnable attention-window scale (physics_models.py:155-182: the
+ *      reference keeps its original trainable logsigma as a comment, :155-161,
+ *      and forms every theta from the scalar, :162-182).  sigma = exp(ln 2 *
+ *      tanh(u)) from one fp32 parameter u, strictly inside (0.5, 2), lives in
+ *      device memory as one double: the host never reads it, so a captured
+ *      step stays valid while it trains.  None of these allocates.
+ *      paig_sigma_from_u writes sigma_dev[0] from u[0] (fp64 tanh / exp; u = 0
+ *      gives exactly 1).  The *_sigma_dev entry points mirror their *_sigma
+ *      namesakes (physics_models.py:155-182) with const double* sigma_dev in
+ *      place of double sigma; the kernels load it once at entry.  The backward
+ *      always runs the generic kernels (their gather window is sized from
+ *      sigma in-kernel; the one-CU kernels' 5-wide tables are chosen on the
+ *      host by sigma >= 1), every target / loss-weight / live mode as in
+ *      paig_decoder_bwd_ex_sigma; slab rows and scratch floats:
+ *      paig_decoder_bwd_blocks_sigma_dev / paig_decoder_bwd_scratch_sigma_dev.
+ *      It additionally writes dsig[F] (nullable: then exactly the other
+ *      outputs): dL/dsigma of every frame in fp64,
+ *        (h/2) sum_k [ sum_p (gx_p bc[j] + gy_p bc[i]) + ((H/2 - x_k)/h) sum_p
+ *        gx_p + ((H/2 - y_k)/h) sum_p gy_p ]
+ *      with gx, gy the pixel gradients of the position gradient and bc the
+ *      affine_grid base coordinates; 0.0 for skipped (dead, weightless) frames.
+ *      paig_sigma_grad sums dsig_a[na] and dsig_b[nb] (either may be empty) in
+ *      a fixed order in fp64, multiplies by d sigma / du = ln 2 sigma (1 -
+ *      tanh(u)^2) and writes the fp32 result to gu[0] (accumulate: adds). */
+int paig_sigma_from_u(const float* u, double* sigma_dev, void* stream);
+int paig_sigma_grad(const double* dsig_a, int na, const double* dsig_b, int nb, const float* u, float* gu,
+                    int accumulate, void* stream);
+int paig_decoder_fwd_sigma_dev(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                               const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
+                               const float* tgt, long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F,
+                               int K, int h, int H, const double* sigma_dev, void* stream);
+int paig_decoder_fwd_rollout_sigma_dev(int cell, const float* pos0, long long pos0_ld, const float* vel0,
+                                       const float* dt, const double* p0, const double* p1, float* pvs, int B, int D,
+                                       int R, const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                                       const float* tmpl, const float* cont, const float* bg, float* out,
+                                       long long out_fs, const float* tgt, long long tgt_fs, int tgt_grp,
+                                       long long tgt_gs, float* sse, int F, int K, int h, int H,
+                                       const double* sigma_dev, void* stream);
+int paig_decoder_fwd_t8_sigma_dev(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                                  const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
+                                  const unsigned char* tgt, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
+                                  long long tgt_gs, float* sse, int F, int K, int h, int H, const double* sigma_dev,
+                                  void* stream);
+int paig_decoder_bwd_blocks_sigma_dev(int F, int K, int h, int H);
+size_t paig_decoder_bwd_scratch_sigma_dev(int F, int K, int h, int H);
+int paig_decoder_bwd_ex_sigma_dev(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                                  const float* tmpl, const float* cont, const float* bg, const float* tgt,
+                                  const unsigned char* tgt8, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
+                                  long long tgt_gs, const float* dsse, int lw_mode, const float* dt, const float* de,
+                                  const float* dr, float ae, int lB, int lTe, int lR, int lpred, const float* dout,
+                                  long long dout_fs, float* dpos, float* slab, float* scratch, int F, int live, int K,
+                                  int h, int H, const double* sigma_dev, double* dsig, void* stream);
+int paig_decoder_parts_sigma_dev(const float* pos, long long pos_inner, const float* tmpl, const float* cont,
+                                 const float* bg, float* contents, float* masks, int F, int K, int h, int H,
+                                 const double* sigma_dev, void* stream);
+
 /* the decoder's per-object intermediates (transf_contents / transf_masks,
  * physics_models.py:186-196) for positions pos [F][2K] (row stride
  * pos_inner): contents [K+1][F][3][H][W] (the K warped sigmoid(content_k)

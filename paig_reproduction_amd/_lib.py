@@ -136,6 +136,17 @@ SIGNATURES = {
     "paig_decoder_bwd_ex_sigma": (I, [P, LL, LL, I, P, P, P, P, P, P, LL, I, LL, P, I, P, P, P, F32, I, I, I, I, P, LL, P,
                                        P, P, I, I, I, I, I, F64, P]),
     "paig_decoder_parts_sigma": (I, [P, LL, P, P, P, P, P, I, I, I, I, F64, P]),
+    "paig_sigma_from_u": (I, [P, P, P]),
+    "paig_sigma_grad": (I, [P, I, P, I, P, P, I, P]),
+    "paig_decoder_fwd_sigma_dev": (I, [P, LL, LL, I, P, P, P, P, LL, P, LL, I, LL, P, I, I, I, I, P, P]),
+    "paig_decoder_fwd_rollout_sigma_dev": (I, [I, P, LL, P, P, P, P, P, I, I, I, P, LL, LL, I, P, P, P, P, LL, P, LL, I,
+                                                LL, P, I, I, I, I, P, P]),
+    "paig_decoder_fwd_t8_sigma_dev": (I, [P, LL, LL, I, P, P, P, P, LL, P, P, LL, I, LL, P, I, I, I, I, P, P]),
+    "paig_decoder_bwd_blocks_sigma_dev": (I, [I, I, I, I]),
+    "paig_decoder_bwd_scratch_sigma_dev": (SZ, [I, I, I, I]),
+    "paig_decoder_bwd_ex_sigma_dev": (I, [P, LL, LL, I, P, P, P, P, P, P, LL, I, LL, P, I, P, P, P, F32, I, I, I, I, P,
+                                           LL, P, P, P, I, I, I, I, I, P, P, P]),
+    "paig_decoder_parts_sigma_dev": (I, [P, LL, P, P, P, P, P, I, I, I, I, P, P]),
     "paig_stn_fwd": (I, [P, P, P, I, I, I, I, I, I, P]),
     "paig_stn_bwd": (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
     "paig_stn_fwd_f64": (I, [P, P, P, I, I, I, I, I, I, P]),
@@ -177,6 +188,7 @@ _QUERY = {"paig_last_error", "paig_abi_version", "paig_f16_range_status", "paig_
           "paig_velmlp_rollout_bwd_workspace",
           "paig_vfn_bwd_blocks", "paig_rollout_bwd_blocks", "paig_decoder_bwd_blocks", "paig_decoder_slab_len",
           "paig_decoder_bwd_scratch", "paig_decoder_bwd_blocks_sigma", "paig_decoder_bwd_scratch_sigma",
+          "paig_decoder_bwd_blocks_sigma_dev", "paig_decoder_bwd_scratch_sigma_dev",
           "paig_grad_norm_chunk", "paig_grad_norm_scratch"}
 
 

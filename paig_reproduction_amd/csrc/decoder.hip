@@ -45,6 +45,15 @@ struct PosView {
   // products theta2, theta5 (:166-167)
   double sg;
   float sgf;
+  // a device-resident sigma (the learnable scale: the host does not know it),
+  // or null: sg / sgf above hold.  Kernels call load() once at entry.
+  const double* sgp = nullptr;
+  __device__ __forceinline__ void load() {
+    if (sgp) {   // uniform: one scalar load
+      sg = *sgp;
+      sgf = (float)sg;
+    }
+  }
   // theta2 / theta5 of an object at l on one axis: fp32 as the reference
   // forms it, widened for the fp64 grid (Q9)
   __device__ __forceinline__ double theta_t(float l, int H, int h) const {
@@ -169,6 +178,7 @@ __device__ __forceinline__ void composite(const float* T, const float* Cn, const
 template <int K>
 __global__ void __launch_bounds__(256)
 dec_fwd_k(PosView pos, Src S, FViewW out, FView tgt, float* __restrict__ sse, int F, int h, int H) {
+  pos.load();
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int hh = h * h, HW = H * H;
   float* T = lds;
@@ -316,6 +326,7 @@ __device__ __forceinline__ void blend(const float (*sv)[4], const float* bgv, fl
 template <int K, int H>
 __global__ void __launch_bounds__(256)
 dec_fwd_reg_k(PosView pos, Src S, FViewW out, FView tgt, float* __restrict__ sse, int F) {
+  pos.load();
   constexpr int h = H / 2, hh = h * h, HW = H * H, PPT = (HW + 255) / 256;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* T = lds;
@@ -679,16 +690,25 @@ struct DecFrames {
 // weight and no dense gradient) get zero position gradients and are not read.
 // Targets (T8) and loss weights (LW) as in the one-CU kernels.
 // slab row layout per block: [K*h*h template | K*3*h*h content | 3*H*W bg]
+//
+// dsig (nullable; the learnable scale, physics_models.py:155-161): dL/dsigma
+// of every frame.  ix_j = ((g_j + 1) h - 1) / 2 with g_j = sigma bc[j] + t_x,
+// t_x = fl32(((H/2 - x_k) / h) fl32(sigma)), so d ix_j / d sigma = (h / 2)
+// (bc[j] + (H/2 - x_k) / h): the pixel gradients gx, gy that feed sx, sy,
+// weighted by the base coordinate, in two more fp64 sums per object, reduced
+// with them; skipped frames get 0.
 template <int K, bool T8, bool LW>
 __global__ void __launch_bounds__(256)
 dec_bwd_k(PosView pos, Src S, TView tgt, WSrc dsse, FView dout, float* __restrict__ dpos,
-          float* __restrict__ slab, float* __restrict__ gscratch, int F, int live, int h, int H) {
+          float* __restrict__ slab, float* __restrict__ gscratch, double* __restrict__ dsig, int F, int live, int h,
+          int H) {
+  pos.load();
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int hh = h * h, HW = H * H;
   float* T = lds;
   float* Cn = T + K * hh;
   float* G = gscratch ? gscratch + (long long)blockIdx.x * K * 4 * HW : Cn + K * 3 * hh;  // [K][4][HW]
-  __shared__ double redd[4][2 * K];
+  __shared__ double redd[4][4 * K];   // sx, sy per object | (dsig) their bc-weighted sums
   __shared__ int skip_s;
   __shared__ float cx[K][MAXH], cy[K][MAXH];
   __shared__ double bc[MAXH];
@@ -724,15 +744,16 @@ dec_bwd_k(PosView pos, Src S, TView tgt, WSrc dsse, FView dout, float* __restric
     __syncthreads();
     if (skip_s) {
       if (threadIdx.x < 2 * K) dpos[(long long)f * 2 * K + threadIdx.x] = 0.f;
+      if (dsig && threadIdx.x == 64) dsig[f] = 0.0;
       __syncthreads();
       continue;
     }
     coord_tables<K>(pos, f, H, h, cx, cy, bc);
     __syncthreads();
     const long long to = has_w ? FR.template tgt_off<T8>(cur) : 0;
-    double sx[K], sy[K];
+    double sx[K], sy[K], bx[K], by[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) sx[k] = sy[k] = 0.0;
+    for (int k = 0; k < K; ++k) sx[k] = sy[k] = bx[k] = by[k] = 0.0;
 
     // ---- pass 1: per-pixel gradients
     for (int p = threadIdx.x; p < HW; p += blockDim.x) {
@@ -773,15 +794,26 @@ dec_bwd_k(PosView pos, Src S, TView tgt, WSrc dsse, FView dout, float* __restric
         }
         sx[k] += (double)gx;
         sy[k] += (double)gy;
+        if (dsig) {
+          bx[k] += (double)gx * bc[j];
+          by[k] += (double)gy * bc[i];
+        }
       }
     }
-    // ---- per-frame dpos reduction (fp64)
+    // ---- per-frame dpos (and dsigma) reduction (fp64)
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       double a = wave_sum_d(sx[k]), b = wave_sum_d(sy[k]);
       if (lane == 0) {
         redd[wv][2 * k] = a;
         redd[wv][2 * k + 1] = b;
+      }
+      if (dsig) {
+        a = wave_sum_d(bx[k]), b = wave_sum_d(by[k]);
+        if (lane == 0) {
+          redd[wv][2 * K + 2 * k] = a;
+          redd[wv][2 * K + 2 * k + 1] = b;
+        }
       }
     }
     __syncthreads();
@@ -791,6 +823,24 @@ dec_bwd_k(PosView pos, Src S, TView tgt, WSrc dsse, FView dout, float* __restric
       // d theta = sum_p dgrid = sum_p dix * h/2 ; dloc = -(dtheta * sigma) / h
       const float dth = (float)(s * (double)h * 0.5);
       dpos[(long long)f * 2 * K + threadIdx.x] = -(dth * pos.sgf) / (float)h;
+    }
+    if (dsig && threadIdx.x == 64) {   // (a wave of its own: beside the position gradients')
+      const float* pf = pos.at(f);
+      double tot = 0.0;
+      for (int k = 0; k < K; ++k) {
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int w = 0; w < nw; ++w) {
+          s[0] += redd[w][2 * k];
+          s[1] += redd[w][2 * k + 1];
+          s[2] += redd[w][2 * K + 2 * k];
+          s[3] += redd[w][2 * K + 2 * k + 1];
+        }
+        // d t / d sigma of the two axes: theta_t's fp32 quotient, widened
+        const double ax = (double)(((float)H / 2.f - pf[2 * k]) / (float)h);
+        const double ay = (double)(((float)H / 2.f - pf[2 * k + 1]) / (float)h);
+        tot += (s[2] + s[3]) + (ax * s[0] + ay * s[1]);
+      }
+      dsig[f] = tot * ((double)h * 0.5);
     }
     // ---- pass 2: gather source gradients from the pixel-gradient image
     for (int s = threadIdx.x; s < K * hh; s += blockDim.x) {
@@ -1676,6 +1726,7 @@ __device__ __forceinline__ int b128_rank(int l) {
 template <int K, int H, bool T8>
 __device__ __forceinline__ void dec_fwd_cu_body(PosView pos, Src S, FViewW out, TView tgt, float* __restrict__ sse, int F,
                                                 int FPB, int bid) {
+  pos.load();
   using C = DecFw<K, H>;
   constexpr int h = C::h, hp = C::hp, HW = C::HW, GPR = C::GPR, NC = C::NC, NW = C::NW, P = C::P;
   __shared__ float4 SRC[K][hp * P];     // (template + 5, sigmoid(content) x 3), zero border, split rows
@@ -1927,6 +1978,7 @@ static int dec_launch_fwd(PosView pv, Src S, FViewW out, TView tgt, float* sse, 
 template <int K>
 __global__ void __launch_bounds__(256)
 dec_parts_k(PosView pos, Src S, float* __restrict__ contents, float* __restrict__ masks, int F, int h, int H) {
+  pos.load();
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int hh = h * h, HW = H * H;
   float* T = lds;
@@ -2065,6 +2117,36 @@ stn_bwd_k(const float* __restrict__ U, const T* __restrict__ th, const float* __
   }
 }
 
+// The learnable attention-window scale (the reference's commented-out
+// trainable logsigma, physics_models.py:155-161): sigma = exp(ln 2 tanh(u))
+// from the fp32 parameter u, in fp64 -- strictly inside (0.5, 2), 1 at u = 0.
+constexpr double LN2 = 0.6931471805599453;   // np.log(2.0)
+
+__global__ void sigma_from_u_k(const float* __restrict__ u, double* __restrict__ sg) {
+  if (threadIdx.x == 0) *sg = exp(LN2 * tanh((double)*u));
+}
+
+// dL/du = (sum of both decoders' per-frame dL/dsigma, fixed order, fp64) *
+// d sigma / du = ln 2 sigma (1 - tanh(u)^2), rounded to fp32 into u's
+// gradient slot (accumulate: added to it)
+__global__ void __launch_bounds__(256)
+sigma_grad_k(const double* __restrict__ a, int na, const double* __restrict__ b, int nb, const float* __restrict__ u,
+             float* __restrict__ gu, int accumulate) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < na; i += 256) s += a[i];
+  for (int i = threadIdx.x; i < nb; i += 256) s += b[i];
+  s = wave_sum_d(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double tot = (red[0] + red[1]) + (red[2] + red[3]);
+    const double t = tanh((double)*u), sg = exp(LN2 * t);
+    const float g = (float)(tot * (LN2 * sg * (1.0 - t * t)));
+    *gu = accumulate ? *gu + g : g;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -2103,6 +2185,13 @@ static bool dec_bwd_cu(int K, int h, int H, double sigma) { return dec_cu_shape(
 
 // Slab rows (= blocks) of the backward over F frames grouped by grp
 // (0: ungrouped) of which the first `live` per group are processed (0: all).
+static int dec_gen_blocks(int F) {   // the generic backward's
+  int g = (F + 1) / 2;
+  if (g > 768) g = 768;   // ~3 blocks per CU: latency hiding for the per-frame passes
+  if (g < 1) g = 1;
+  return g;
+}
+
 int paig_decoder_bwd_blocks_sigma(int F, int grp, int live, int K, int h, int H, double sigma) {
   if (F <= 0) return 1;
   if (dec_bwd_cu(K, h, H, sigma)) {
@@ -2110,11 +2199,11 @@ int paig_decoder_bwd_blocks_sigma(int F, int grp, int live, int K, int h, int H,
     const int g = NL > 0 ? cdiv(NL, dec_cu_fpb(NL)) : 1;
     return g < 1 ? 1 : g;
   }
-  int g = (F + 1) / 2;
-  if (g > 768) g = 768;   // ~3 blocks per CU: latency hiding for the per-frame passes
-  if (g < 1) g = 1;
-  return g;
+  return dec_gen_blocks(F);
 }
+
+// a device-resident sigma: always the generic backward (every frame walked)
+int paig_decoder_bwd_blocks_sigma_dev(int F, int K, int h, int H) { return F <= 0 ? 1 : dec_gen_blocks(F); }
 
 int paig_decoder_bwd_blocks(int F, int grp, int live, int K, int h, int H) {
   return paig_decoder_bwd_blocks_sigma(F, grp, live, K, h, H, 1.0);
@@ -2124,12 +2213,18 @@ size_t paig_decoder_slab_len(int K, int h, int H) { return (size_t)K * h * h * 4
 
 // Global scratch (floats) needed when the per-frame pixel-gradient image does
 // not fit LDS; 0 when it does.
-size_t paig_decoder_bwd_scratch_sigma(int F, int K, int h, int H, double sigma) {
-  if (dec_bwd_cu(K, h, H, sigma)) return 0;
+static size_t dec_gen_scratch(int F, int K, int h, int H) {
   size_t lds = ((size_t)K * h * h * 4 + (size_t)K * 4 * H * H) * 4;
   if (lds <= 120 * 1024) return 0;
-  return (size_t)paig_decoder_bwd_blocks_sigma(F, 0, 0, K, h, H, sigma) * K * 4 * H * H;
+  return (size_t)(F <= 0 ? 1 : dec_gen_blocks(F)) * K * 4 * H * H;
 }
+
+size_t paig_decoder_bwd_scratch_sigma(int F, int K, int h, int H, double sigma) {
+  if (dec_bwd_cu(K, h, H, sigma)) return 0;
+  return dec_gen_scratch(F, K, h, H);
+}
+
+size_t paig_decoder_bwd_scratch_sigma_dev(int F, int K, int h, int H) { return dec_gen_scratch(F, K, h, H); }
 
 size_t paig_decoder_bwd_scratch(int F, int K, int h, int H) { return paig_decoder_bwd_scratch_sigma(F, K, h, H, 1.0); }
 
@@ -2137,11 +2232,12 @@ size_t paig_decoder_bwd_scratch(int F, int K, int h, int H) { return paig_decode
 
 static int dec_fwd(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
                    const float* cont, const float* bg, float* out, long long out_fs, TView t, float* sse, int F, int K,
-                   int h, int H, double sigma, void* stream) {
-  PAIG_REQUIRE(dec_sigma_ok(sigma), "decoder: sigma=%g outside [0.5, 2]", sigma);
+                   int h, int H, double sigma, const double* sgp, void* stream) {
+  // sgp: sigma read from device memory by the kernels (`sigma` is then unused)
+  PAIG_REQUIRE(sgp || dec_sigma_ok(sigma), "decoder: sigma=%g outside [0.5, 2]", sigma);
   if (F <= 0) return 0;
   PAIG_REQUIRE(H == 2 * h, "decoder: H=%d must be 2*tmpl=%d", H, 2 * h);
-  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma};
+  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma, sgp};
   Src S{tmpl, cont, bg};
   FViewW o{out, out_fs};
   hipStream_t st = (hipStream_t)stream;
@@ -2154,8 +2250,11 @@ static int dec_fwd(const float* pos, long long pos_outer, long long pos_inner, i
 static int dec_bwd(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
                    const float* cont, const float* bg, TView t, WSrc dsse, const float* dout,
                    long long dout_fs, float* dpos, float* slab, float* scratch, int F, int live, int K, int h, int H,
-                   double sigma, void* stream) {
-  PAIG_REQUIRE(dec_sigma_ok(sigma), "decoder_bwd: sigma=%g outside [0.5, 2]", sigma);
+                   double sigma, const double* sgp, double* dsig, void* stream) {
+  // sgp: sigma read from device memory (`sigma` unused): the generic kernels,
+  // whose gather window is sized in-kernel; dsig (with sgp only): dL/dsigma [F]
+  PAIG_REQUIRE(sgp || dec_sigma_ok(sigma), "decoder_bwd: sigma=%g outside [0.5, 2]", sigma);
+  PAIG_REQUIRE(sgp || !dsig, "decoder_bwd: dL/dsigma needs a device-resident sigma");
   if (F <= 0) return 0;
   PAIG_REQUIRE(dsse.mode >= 0 && dsse.mode <= 2 && (dsse.mode == 0 || (dsse.B > 0 && dsse.Te > 0 && dsse.R > 0)),
                "decoder_bwd: loss-weight mode %d", dsse.mode);
@@ -2170,11 +2269,11 @@ static int dec_bwd(const float* pos, long long pos_outer, long long pos_inner, i
   // generic ones walk them (zero contribution), so both give the same result
   PAIG_REQUIRE(live == 0 || dout == nullptr, "decoder_bwd: live=%d with a dense dL/dout (dead frames would be skipped)",
                live);
-  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma};
+  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma, sgp};
   Src S{tmpl, cont, bg};
   FView d{dout, dout_fs, 0, 0};
   hipStream_t st = (hipStream_t)stream;
-  if (dec_bwd_cu(K, h, H, sigma)) {
+  if (!sgp && dec_bwd_cu(K, h, H, sigma)) {
     const int NL = dec_live(F, pos_grp, live);
     const int fpb = dec_cu_fpb(NL > 0 ? NL : 1);
     const int g = paig_decoder_bwd_blocks_sigma(F, pos_grp, live, K, h, H, sigma);
@@ -2208,8 +2307,8 @@ static int dec_bwd(const float* pos, long long pos_outer, long long pos_inner, i
   PAIG_REQUIRE(dsse.mode == 0 || dec_cu_shape(K, h, H),
                "decoder_bwd: in-kernel loss weights need the one-CU kernels (K=%d H=%d)", K, H);
   // generic kernels: every frame is walked (dead ones skipped by their step or zero weight)
-  const int g = paig_decoder_bwd_blocks_sigma(F, 0, 0, K, h, H, sigma);
-  const bool need_scratch = paig_decoder_bwd_scratch_sigma(F, K, h, H, sigma) > 0;
+  const int g = dec_gen_blocks(F);
+  const bool need_scratch = dec_gen_scratch(F, K, h, H) > 0;
   PAIG_REQUIRE(!need_scratch || scratch, "decoder_bwd: scratch required");
   const int lds = (K * h * h * 4 + (need_scratch ? 0 : K * 4 * H * H)) * 4;
   float* gs = need_scratch ? scratch : nullptr;
@@ -2221,7 +2320,7 @@ static int dec_bwd(const float* pos, long long pos_outer, long long pos_inner, i
     constexpr bool T8 = decltype(t8)::value, LW = decltype(lw)::value;
     auto go = [&](auto kern) {
       if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      hipLaunchKernelGGL(kern, dim3(g), dim3(256), lds, st, pv, S, t, dsse, d, dpos, slab, gs, F, live, h, H);
+      hipLaunchKernelGGL(kern, dim3(g), dim3(256), lds, st, pv, S, t, dsse, d, dpos, slab, gs, dsig, F, live, h, H);
     };
     if (K == 2) go(dec_bwd_k<2, T8, LW>);
     else go(dec_bwd_k<3, T8, LW>);
@@ -2249,7 +2348,19 @@ int paig_decoder_fwd_sigma(const float* pos, long long pos_outer, long long pos_
                            long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H,
                            double sigma, void* stream) {
   return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
-                 TView{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, sigma, stream);
+                 TView{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, sigma, nullptr, stream);
+}
+
+// The *_sigma_dev entry points: the *_sigma ones with sigma read by the
+// kernels from device memory (const double* sigma_dev, one element: the
+// learnable scale of physics_models.py:155-161, which the host never sees).
+int paig_decoder_fwd_sigma_dev(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                               const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
+                               const float* tgt, long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F,
+                               int K, int h, int H, const double* sigma_dev, void* stream) {
+  PAIG_REQUIRE(sigma_dev, "decoder_fwd_sigma_dev: a device sigma is required");
+  return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
+                 TView{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, 1.0, sigma_dev, stream);
 }
 
 int paig_decoder_fwd(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
@@ -2264,20 +2375,20 @@ int paig_decoder_fwd(const float* pos, long long pos_outer, long long pos_inner,
 // (paig_decoder_fwd's, fp32 targets and an SSE output) in one launch, where
 // the one-CU decoder serves the shape: (K, H) in {(2, 32), (3, 36), (2, 64)}
 // with 16-byte aligned frames; the cell / D pairs of paig_rollout_fwd.
-int paig_decoder_fwd_rollout_sigma(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
-                                   const double* p0, const double* p1, float* pvs, int B, int D, int R,
-                                   const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
-                                   const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
-                                   const float* tgt, long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F,
-                                   int K, int h, int H, double sigma, void* stream) {
-  PAIG_REQUIRE(dec_sigma_ok(sigma), "decoder_fwd_rollout: sigma=%g outside [0.5, 2]", sigma);
+static int dec_fwd_rollout(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
+                           const double* p0, const double* p1, float* pvs, int B, int D, int R, const float* pos,
+                           long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl, const float* cont,
+                           const float* bg, float* out, long long out_fs, const float* tgt, long long tgt_fs,
+                           int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H, double sigma,
+                           const double* sgp, void* stream) {
+  PAIG_REQUIRE(sgp || dec_sigma_ok(sigma), "decoder_fwd_rollout: sigma=%g outside [0.5, 2]", sigma);
   PAIG_REQUIRE(B > 0 && F > 0 && R > 0, "decoder_fwd_rollout: B=%d F=%d R=%d", B, F, R);
   PAIG_REQUIRE(cell == 1 || (p0 && p1), "decoder_fwd_rollout: physics params required");
   PAIG_REQUIRE(H == 2 * h && sse && tgt, "decoder_fwd_rollout: H=%d tmpl=%d, targets and an SSE output required", H, h);
   const bool al = ((uintptr_t)out | (uintptr_t)bg | (uintptr_t)tgt) % 16 == 0 && out_fs % 4 == 0 && tgt_fs % 4 == 0 &&
                   tgt_gs % 4 == 0;
   PAIG_REQUIRE(al, "decoder_fwd_rollout: 16-byte aligned frames required");
-  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma};
+  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma, sgp};
   Src S{tmpl, cont, bg};
   FViewW o{out, out_fs};
   TView t{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp};
@@ -2309,6 +2420,28 @@ int paig_decoder_fwd_rollout_sigma(int cell, const float* pos0, long long pos0_l
   return 0;
 }
 
+int paig_decoder_fwd_rollout_sigma(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
+                                   const double* p0, const double* p1, float* pvs, int B, int D, int R,
+                                   const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                                   const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
+                                   const float* tgt, long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F,
+                                   int K, int h, int H, double sigma, void* stream) {
+  return dec_fwd_rollout(cell, pos0, pos0_ld, vel0, dt, p0, p1, pvs, B, D, R, pos, pos_outer, pos_inner, pos_grp, tmpl,
+                         cont, bg, out, out_fs, tgt, tgt_fs, tgt_grp, tgt_gs, sse, F, K, h, H, sigma, nullptr, stream);
+}
+
+int paig_decoder_fwd_rollout_sigma_dev(int cell, const float* pos0, long long pos0_ld, const float* vel0,
+                                       const float* dt, const double* p0, const double* p1, float* pvs, int B, int D,
+                                       int R, const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                                       const float* tmpl, const float* cont, const float* bg, float* out,
+                                       long long out_fs, const float* tgt, long long tgt_fs, int tgt_grp,
+                                       long long tgt_gs, float* sse, int F, int K, int h, int H,
+                                       const double* sigma_dev, void* stream) {
+  PAIG_REQUIRE(sigma_dev, "decoder_fwd_rollout_sigma_dev: a device sigma is required");
+  return dec_fwd_rollout(cell, pos0, pos0_ld, vel0, dt, p0, p1, pvs, B, D, R, pos, pos_outer, pos_inner, pos_grp, tmpl,
+                         cont, bg, out, out_fs, tgt, tgt_fs, tgt_grp, tgt_gs, sse, F, K, h, H, 1.0, sigma_dev, stream);
+}
+
 int paig_decoder_fwd_rollout(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
                              const double* p0, const double* p1, float* pvs, int B, int D, int R, const float* pos,
                              long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
@@ -2327,7 +2460,19 @@ int paig_decoder_fwd_t8_sigma(const float* pos, long long pos_outer, long long p
   PAIG_REQUIRE(tgt && sse, "decoder_fwd_t8: byte targets and an SSE output are required");
   PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_fwd_t8: a row index needs grouped targets");
   return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
-                 TView{nullptr, tgt, tgt_idx, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, sigma, stream);
+                 TView{nullptr, tgt, tgt_idx, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, sigma, nullptr, stream);
+}
+
+int paig_decoder_fwd_t8_sigma_dev(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                                  const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
+                                  const unsigned char* tgt, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
+                                  long long tgt_gs, float* sse, int F, int K, int h, int H, const double* sigma_dev,
+                                  void* stream) {
+  PAIG_REQUIRE(tgt && sse, "decoder_fwd_t8: byte targets and an SSE output are required");
+  PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_fwd_t8: a row index needs grouped targets");
+  PAIG_REQUIRE(sigma_dev, "decoder_fwd_t8_sigma_dev: a device sigma is required");
+  return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
+                 TView{nullptr, tgt, tgt_idx, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, 1.0, sigma_dev, stream);
 }
 
 int paig_decoder_fwd_t8(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
@@ -2344,7 +2489,7 @@ int paig_decoder_bwd(const float* pos, long long pos_outer, long long pos_inner,
                      float* slab, float* scratch, int F, int live, int K, int h, int H, void* stream) {
   return dec_bwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, TView{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp},
                  WSrc{dsse, nullptr, nullptr, nullptr, 0.f, 0, 0, 0, 0, 0}, dout, dout_fs, dpos, slab, scratch, F, live, K, h,
-                 H, 1.0, stream);
+                 H, 1.0, nullptr, nullptr, stream);
 }
 
 int paig_decoder_bwd_t8(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
@@ -2356,7 +2501,7 @@ int paig_decoder_bwd_t8(const float* pos, long long pos_outer, long long pos_inn
   PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_bwd_t8: a row index needs grouped targets");
   return dec_bwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, TView{nullptr, tgt, tgt_idx, tgt_fs, tgt_gs, tgt_grp},
                  WSrc{dsse, nullptr, nullptr, nullptr, 0.f, 0, 0, 0, 0, 0}, dout, dout_fs, dpos, slab, scratch, F, live, K, h,
-                 H, 1.0, stream);
+                 H, 1.0, nullptr, nullptr, stream);
 }
 
 // The backward with either target form (tgt fp32, or tgt8 + tgt_idx bytes:
@@ -2379,7 +2524,45 @@ int paig_decoder_bwd_ex_sigma(const float* pos, long long pos_outer, long long p
                lR);
   return dec_bwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, TView{tgt, tgt8, tgt8 ? tgt_idx : nullptr, tgt_fs, tgt_gs, tgt_grp},
                  WSrc{lw_mode ? nullptr : dsse, dt, de, dr, ae, lB, lTe, lR, lpred, lw_mode}, dout, dout_fs, dpos, slab,
-                 scratch, F, live, K, h, H, sigma, stream);
+                 scratch, F, live, K, h, H, sigma, nullptr, nullptr, stream);
+}
+
+// paig_decoder_bwd_ex_sigma with sigma in device memory: always the generic
+// kernels (slab rows / scratch: paig_decoder_bwd_blocks_sigma_dev /
+// _bwd_scratch_sigma_dev), and dsig (nullable) [F]: every frame's dL/dsigma in
+// fp64, 0.0 for the frames the launch skips (dead or weightless).
+int paig_decoder_bwd_ex_sigma_dev(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
+                                  const float* tmpl, const float* cont, const float* bg, const float* tgt,
+                                  const unsigned char* tgt8, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
+                                  long long tgt_gs, const float* dsse, int lw_mode, const float* dt, const float* de,
+                                  const float* dr, float ae, int lB, int lTe, int lR, int lpred, const float* dout,
+                                  long long dout_fs, float* dpos, float* slab, float* scratch, int F, int live, int K,
+                                  int h, int H, const double* sigma_dev, double* dsig, void* stream) {
+  PAIG_REQUIRE(!tgt != !tgt8, "decoder_bwd_ex: exactly one of the fp32 / byte targets");
+  PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_bwd_ex: a row index needs grouped targets");
+  PAIG_REQUIRE(lw_mode != 0 || !dt, "decoder_bwd_ex: loss adjoints given with lw_mode 0");
+  PAIG_REQUIRE(lw_mode != 2 || (pos_grp == lR && F % lR == 0), "decoder_bwd_ex: rollout weights need frames grouped by R=%d",
+               lR);
+  PAIG_REQUIRE(sigma_dev, "decoder_bwd_ex_sigma_dev: a device sigma is required");
+  return dec_bwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, TView{tgt, tgt8, tgt8 ? tgt_idx : nullptr, tgt_fs, tgt_gs, tgt_grp},
+                 WSrc{lw_mode ? nullptr : dsse, dt, de, dr, ae, lB, lTe, lR, lpred, lw_mode}, dout, dout_fs, dpos, slab,
+                 scratch, F, live, K, h, H, 1.0, sigma_dev, dsig, stream);
+}
+
+int paig_sigma_from_u(const float* u, double* sigma_dev, void* stream) {
+  PAIG_REQUIRE(u && sigma_dev, "sigma_from_u: null argument");
+  hipLaunchKernelGGL(sigma_from_u_k, dim3(1), dim3(64), 0, (hipStream_t)stream, u, sigma_dev);
+  PAIG_CHECK_LAUNCH();
+  return 0;
+}
+
+int paig_sigma_grad(const double* dsig_a, int na, const double* dsig_b, int nb, const float* u, float* gu,
+                    int accumulate, void* stream) {
+  PAIG_REQUIRE(u && gu && na >= 0 && nb >= 0 && (na == 0 || dsig_a) && (nb == 0 || dsig_b), "sigma_grad: bad argument");
+  hipLaunchKernelGGL(sigma_grad_k, dim3(1), dim3(256), 0, (hipStream_t)stream, dsig_a, na, dsig_b, nb, u, gu,
+                     accumulate);
+  PAIG_CHECK_LAUNCH();
+  return 0;
 }
 
 int paig_decoder_bwd_ex(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
@@ -2420,13 +2603,13 @@ static int stn_bwd(const float* U, const T* theta, const float* dout, float* dU,
 
 extern "C" {
 
-int paig_decoder_parts_sigma(const float* pos, long long pos_inner, const float* tmpl, const float* cont,
-                             const float* bg, float* contents, float* masks, int F, int K, int h, int H, double sigma,
-                             void* stream) {
-  PAIG_REQUIRE(dec_sigma_ok(sigma), "decoder_parts: sigma=%g outside [0.5, 2]", sigma);
+static int dec_parts(const float* pos, long long pos_inner, const float* tmpl, const float* cont, const float* bg,
+                     float* contents, float* masks, int F, int K, int h, int H, double sigma, const double* sgp,
+                     void* stream) {
+  PAIG_REQUIRE(sgp || dec_sigma_ok(sigma), "decoder_parts: sigma=%g outside [0.5, 2]", sigma);
   if (F <= 0) return 0;
   PAIG_REQUIRE(H == 2 * h && H <= MAXH, "decoder_parts: H=%d must be 2*tmpl=%d (<= %d)", H, 2 * h, MAXH);
-  PosView pv{pos, 0, pos_inner, 0, sigma, (float)sigma};
+  PosView pv{pos, 0, pos_inner, 0, sigma, (float)sigma, sgp};
   Src S{tmpl, cont, bg};
   hipStream_t st = (hipStream_t)stream;
   const int g = F < 2048 ? F : 2048;
@@ -2439,6 +2622,19 @@ int paig_decoder_parts_sigma(const float* pos, long long pos_inner, const float*
   }
   PAIG_CHECK_LAUNCH();
   return 0;
+}
+
+int paig_decoder_parts_sigma(const float* pos, long long pos_inner, const float* tmpl, const float* cont,
+                             const float* bg, float* contents, float* masks, int F, int K, int h, int H, double sigma,
+                             void* stream) {
+  return dec_parts(pos, pos_inner, tmpl, cont, bg, contents, masks, F, K, h, H, sigma, nullptr, stream);
+}
+
+int paig_decoder_parts_sigma_dev(const float* pos, long long pos_inner, const float* tmpl, const float* cont,
+                                 const float* bg, float* contents, float* masks, int F, int K, int h, int H,
+                                 const double* sigma_dev, void* stream) {
+  PAIG_REQUIRE(sigma_dev, "decoder_parts_sigma_dev: a device sigma is required");
+  return dec_parts(pos, pos_inner, tmpl, cont, bg, contents, masks, F, K, h, H, 1.0, sigma_dev, stream);
 }
 
 int paig_decoder_parts(const float* pos, long long pos_inner, const float* tmpl, const float* cont, const float* bg,

@@ -264,6 +264,8 @@ class StepState:
     sw: Switches = None         # new_state: the forward's A/B switches; every stage
     x_view: tuple = None        # new_state: the encoder's frames (pointer, stride, group, group stride)
     sigma: float = 1.0          # forward: the decoders' window scale (model.decoder_sigma()); forward, backward
+    sigma_dev: object = None    # forward (learn_sigma, else None): the model's one-double device sigma, written by
+    #                             paig_sigma_from_u at the start of the forward; the decoders' forward and backward
     tb: int = 0                 # forward: 1 = the rollout targets are dataset bytes; backward
     tgt_roll: tuple = None      # forward: the rollout decoders' target view; backward
     src: dict = None            # forward: VFN buffers {name: (hidden, raw, post-sigmoid or None)}; backward
@@ -482,11 +484,19 @@ class Engine:
         lay = Layout(model, B, T, read_switches())
         L = self.L
         x = x.contiguous()
-        sigma = model.decoder_sigma()   # log_sig is read at every forward, as in the reference
+        learn = getattr(model, "learn_sigma", False)
+        # log_sig is read at every forward, as in the reference; the learnable
+        # scale is never read by the host (decoder_sigma() would synchronise)
+        sigma = 1.0 if learn else model.decoder_sigma()
         S = self.new_state(lay, x, need_saved)
-        S.sigma = self.last_sigma = sigma
+        S.sigma = sigma
         dev, ws, sw = S.dev, S.ws, S.sw
         st = stream_handle(dev)
+        if learn:   # sigma from u, on the step's stream: captured with the graph
+            S.sigma_dev = model.sigma_buffer()
+            L.paig_sigma_from_u(ptr(self.p("decoder_sigma_u")), ptr(S.sigma_dev), st)
+        self.last_sigma = S.sigma_dev if learn else sigma
+        sg_arg, sg_sfx = (ptr(S.sigma_dev), "_sigma_dev") if learn else (S.sigma, "_sigma")
         K, F, HW, H, h, D = lay.K, lay.F, lay.HW, lay.H, lay.h, lay.D
 
         # ---- VariableFromNetwork sources (once per step, Q12; only the decoders read them)
@@ -525,7 +535,7 @@ class Engine:
         roll = self._rollout_args(S)
         vel_act = (ptr(S.Xv), ptr(S.v1), ptr(S.v2), ptr(S.vel0))
         dec = (ptr(enc_pos), 0, 2 * K, 0, ptr(tmpl), ptr(cont), ptr(bgp), ptr(recons), lay.frame, *S.x_view,
-               ptr(sse_rec), F, K, h, H, S.sigma)
+               ptr(sse_rec), F, K, h, H, sg_arg)
         # velocity MLP + VFN sources in one launch (independent); then the
         # rollout and the reconstruction decode in one launch
         fuse_vfn = S.vel0 is not None and not lay.alt_vel and sw.fuse_vfn
@@ -545,17 +555,17 @@ class Engine:
         # reconstruction decode (all B*Te frames, SSE vs input fused)
         with self._p("dec_fwd:recon+rollout" if merge_roll else "dec_fwd:recon", 0, self._dec_bytes(F, lay)):
             if merge_roll:
-                L.paig_decoder_fwd_rollout_sigma(*roll, *dec, st)
+                getattr(L, "paig_decoder_fwd_rollout" + sg_sfx)(*roll, *dec, st)
             else:
-                L.paig_decoder_fwd_sigma(*dec, st)
+                getattr(L, "paig_decoder_fwd" + sg_sfx)(*dec, st)
 
         # ---- rollout decode (all B*R frames in one launch, SSE vs input[:, ins:])
         out = _empty(B * lay.R * lay.frame, dev)
         sse_roll = _empty(B * lay.R, dev)
-        dec_fwd = L.paig_decoder_fwd_t8_sigma if S.tb else L.paig_decoder_fwd_sigma
+        dec_fwd = getattr(L, ("paig_decoder_fwd_t8" if S.tb else "paig_decoder_fwd") + sg_sfx)
         with self._p("dec_fwd:rollout", 0, self._dec_bytes(B * lay.R, lay, S.tb or 4)):
             dec_fwd(ptr(S.pvs) + 2 * D * 4, (lay.R + 1) * 2 * D, 2 * D, lay.R, ptr(tmpl), ptr(cont), ptr(bgp),
-                    ptr(out), lay.frame, *S.tgt_roll, ptr(sse_roll), B * lay.R, K, h, H, S.sigma, st)
+                    ptr(out), lay.frame, *S.tgt_roll, ptr(sse_roll), B * lay.R, K, h, H, sg_arg, st)
 
         masks, objs = S.masks, S.objs
         res = {
@@ -764,10 +774,12 @@ class Engine:
         return dt, None, None
 
     # -- backward --------------------------------------------------------
-    def _decoder_bwd(self, S, pos, po, pi, pg, tgt, dsse, lw, dout, dpos, slab_p, scr, nfr, live, st):
+    def _decoder_bwd(self, S, pos, po, pi, pg, tgt, dsse, lw, dout, dpos, slab_p, scr, nfr, live, st, dsig=None):
         """paig_decoder_bwd_ex_sigma (the forward's sigma) over nfr frames at positions (pos, po, pi, pg):
         fp32 (4-tuple) or byte (5-tuple) targets tgt; lw: in-kernel loss
-        weights (mode, LossAdjoints) or None (dsse read)."""
+        weights (mode, LossAdjoints) or None (dsse read).  Learnable sigma
+        (S.sigma_dev): paig_decoder_bwd_ex_sigma_dev, which also writes the
+        frames' dL/dsigma to dsig (a device address)."""
         lay = S.lay
         tf, t8, ti = (tgt[0], None, None) if len(tgt) == 4 else (None, tgt[0], tgt[1])
         fs, grp, gs = tgt[-3:]
@@ -777,10 +789,13 @@ class Engine:
             dsse = None
         else:
             lwa = (0, None, None, None, 0.0, 0, 0, 0, 0)
-        self.L.paig_decoder_bwd_ex_sigma(pos, po, pi, pg, ptr(S.src["var_net_template"][1]),
-                                         ptr(S.src["var_net_content"][1]), ptr(S.src["var_net_background"][2]), tf, t8,
-                                         ti, fs, grp, gs, ptr(dsse), *lwa, ptr(dout), lay.frame, dpos, slab_p, scr, nfr,
-                                         live, lay.K, lay.h, lay.H, S.sigma, st)
+        args = (pos, po, pi, pg, ptr(S.src["var_net_template"][1]), ptr(S.src["var_net_content"][1]),
+                ptr(S.src["var_net_background"][2]), tf, t8, ti, fs, grp, gs, ptr(dsse), *lwa, ptr(dout), lay.frame,
+                dpos, slab_p, scr, nfr, live, lay.K, lay.h, lay.H)
+        if S.sigma_dev is not None:
+            self.L.paig_decoder_bwd_ex_sigma_dev(*args, ptr(S.sigma_dev), dsig, st)
+        else:
+            self.L.paig_decoder_bwd_ex_sigma(*args, S.sigma, st)
 
     def backward(self, S, d_sse_rec=None, d_sse_roll=None, d_out=None, d_recons=None, d_enc_pos=None, d_pvs=None,
                  roll_live=0, lossw=None):
@@ -811,11 +826,23 @@ class Engine:
         # ---- buffers of the whole decoder / rollout / velocity backward
         slab_len = int(L.paig_decoder_slab_len(K, h, H))
         roll_live = roll_live if (d_out is None and 0 < roll_live < R) else 0
-        nb_rec = L.paig_decoder_bwd_blocks_sigma(F, 0, 0, K, h, H, S.sigma)
-        nb_roll = L.paig_decoder_bwd_blocks_sigma(B * R, R, roll_live, K, h, H, S.sigma)
+        learn = S.sigma_dev is not None
+        dsig_rec = dsig_roll = None
+        if learn:
+            # the generic backward (the host cannot choose a kernel by a sigma
+            # it does not know); every frame's dL/dsigma, both decoders' arrays
+            nb_rec = L.paig_decoder_bwd_blocks_sigma_dev(F, K, h, H)
+            nb_roll = L.paig_decoder_bwd_blocks_sigma_dev(B * R, K, h, H)
+            scr_n = max(L.paig_decoder_bwd_scratch_sigma_dev(F, K, h, H),
+                        L.paig_decoder_bwd_scratch_sigma_dev(B * R, K, h, H))
+            dsig = _empty(F + B * R, dev, torch.float64)
+            dsig_rec, dsig_roll = ptr(dsig), ptr(dsig) + F * 8
+        else:
+            nb_rec = L.paig_decoder_bwd_blocks_sigma(F, 0, 0, K, h, H, S.sigma)
+            nb_roll = L.paig_decoder_bwd_blocks_sigma(B * R, R, roll_live, K, h, H, S.sigma)
+            scr_n = max(L.paig_decoder_bwd_scratch_sigma(F, K, h, H, S.sigma),
+                        L.paig_decoder_bwd_scratch_sigma(B * R, K, h, H, S.sigma))
         slab = _empty((nb_rec + nb_roll) * slab_len, dev)
-        scr_n = max(L.paig_decoder_bwd_scratch_sigma(F, K, h, H, S.sigma),
-                    L.paig_decoder_bwd_scratch_sigma(B * R, K, h, H, S.sigma))
         scratch = _empty(scr_n, dev) if scr_n else None
         denc = _empty(F * D, dev)   # d enc_pos [B][Te][D]
         dpos_roll = _empty(B * R * D, dev)
@@ -840,7 +867,7 @@ class Engine:
         with self._p("dec_bwd:rollout", 0, self._dec_bwd_bytes(live_frames, B * R, lay, d_out is not None, S.tb or 4)):
             self._decoder_bwd(S, ptr(S.pvs) + 2 * D * 4, (R + 1) * 2 * D, 2 * D, R, S.tgt_roll, d_sse_roll,
                               lossw.get("roll"), d_out, ptr(dpos_roll), ptr(slab) + nb_rec * slab_len * 4,
-                              ptr(scratch), B * R, roll_live, st)
+                              ptr(scratch), B * R, roll_live, st, dsig_roll)
 
         # ---- rollout adjoint -> d pos0, d vel0, physics params; velocity encoder backward
         prm = self.cell_params(lay)
@@ -866,7 +893,10 @@ class Engine:
         # ---- reconstruction decoder backward: d enc_pos + partial source grads
         with self._p("dec_bwd:recon", 0, self._dec_bwd_bytes(F, F, lay, d_recons is not None)):
             self._decoder_bwd(S, ptr(S.enc_pos), 0, 2 * K, 0, S.x_view, d_sse_rec, lossw.get("rec"), d_recons,
-                              ptr(denc), ptr(slab), ptr(scratch), F, 0, st)
+                              ptr(denc), ptr(slab), ptr(scratch), F, 0, st, dsig_rec)
+        if learn:   # both decoders' dL/dsigma -> d loss / du (chain rule), into u's flat gradient slot
+            L.paig_sigma_grad(dsig_rec, F, dsig_roll, B * R, ptr(self.p("decoder_sigma_u")),
+                              ptr(self.g("decoder_sigma_u")), 0, st)
 
         # ---- source-gradient reduction (both decoders' slab rows), then the VFN
         # backward: whole, or phase 1 here and phase 2 inside the head backward's launch

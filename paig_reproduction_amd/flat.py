@@ -21,7 +21,8 @@ from ._lib import GN_COEF, GN_COLS, GN_GROUP0, GN_GROUPS, GN_NONFINITE, GN_NORM,
 # their order is the group id of the segment table
 GROUPS = ("unet", "localiser", "velocity", "decoder", "physics")
 _GROUP_PREFIXES = (("encoder.shallow_unet.", "unet"), ("encoder.unet.", "unet"), ("encoder.", "localiser"),
-                   ("velocity_encoder.", "velocity"), ("var_net_", "decoder"), ("rollout_cell.", "physics"))
+                   ("velocity_encoder.", "velocity"), ("var_net_", "decoder"), ("decoder_sigma_u", "decoder"),
+                   ("rollout_cell.", "physics"))
 assert len(GROUPS) <= GN_GROUPS
 
 

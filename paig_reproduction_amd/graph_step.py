@@ -27,7 +27,12 @@ class GraphStep:
         self.eng = model._native()
         self.one = None
         self.graph = None
-        self.sigma = None   # the decoder window scale the graph was captured with (a kernel argument)
+        # the decoder window scale the graph was captured with (a kernel
+        # argument); a learnable scale lives in device memory: one capture
+        # stays valid while it trains, and the host never reads it
+        self.sigma = None
+        self.learn_sigma = bool(getattr(model, "learn_sigma", False))
+        self.captures = 0
         self.replays = 0
 
     def body(self, x):
@@ -51,7 +56,8 @@ class GraphStep:
         if not self.use_graph:
             return
         m, eng = self.m, self.eng
-        self.sigma = m.decoder_sigma()
+        self.sigma = None if self.learn_sigma else m.decoder_sigma()
+        self.captures += 1
         if self.one is None:   # the seed gradient must exist before any capture
             self.one = torch.ones((), device=self.xbuf.device)
         torch.cuda.synchronize()
@@ -90,7 +96,7 @@ class GraphStep:
     def __call__(self):
         if self.graph is None:
             return self.eager()
-        if self.m.decoder_sigma() != self.sigma:   # log_sig changed since the capture: capture again
+        if not self.learn_sigma and self.m.decoder_sigma() != self.sigma:   # log_sig changed since the capture: capture again
             self.graph = None
             self.capture()
         gs, lg = self.graph

@@ -194,6 +194,8 @@ class BaseNetTorch(torch.nn.Module):
                 self.run_extra_fns("train")
                 if step % print_interval == 0:
                     norms = self._grad_norm_metrics()
+                    if getattr(self, "learn_sigma", False):   # one device read, at the print interval only
+                        self.train_metrics["decoder_sigma"] = self.decoder_sigma()
                     log_metrics(logger, "train - iter=%s" % step, self.train_metrics)
                     if hasattr(self, "check_numerics"):
                         self.check_numerics()

@@ -253,8 +253,10 @@ class PhysicsNet(BaseNetTorch):
                  encoder_type="",
                  decoder_type="conv_st_decoder",
                  device=torch.device("cpu"),
-                 sigma=1.0):
+                 sigma=1.0,
+                 learn_sigma=False):
         super().__init__()
+        self.learn_sigma = False
         self.device = device
         assert task in COORD_UNITS
         self.task = task
@@ -295,6 +297,14 @@ class PhysicsNet(BaseNetTorch):
         # plain attribute (no parameter, not in the state_dict), read at every
         # forward (decoder_sigma)
         self.log_sig = sigma
+        if learn_sigma:
+            # the reference's original trainable logsigma (physics_models.py:
+            # 155-161, kept there as a comment): sigma = exp(ln 2 tanh(u)) from
+            # one fp32 parameter u, strictly inside SIGMA_RANGE for every u
+            lo, hi = self.SIGMA_RANGE
+            if not lo < float(sigma) < hi:
+                raise ValueError(f"sigma={sigma!r}: a learnable sigma starts strictly inside ({lo}, {hi})")
+            u0 = np.arctanh(np.log(np.float64(sigma)) / np.log(2.0))
         # Network subcomponents (creation order = reference order, for init parity)
         self.var_net_content = VariableFromNetwork([self.n_objs, self.conv_ch, tmpl_size, tmpl_size])
         self.var_net_background = VariableFromNetwork([1, *self.input_shape])
@@ -303,6 +313,12 @@ class PhysicsNet(BaseNetTorch):
         self.velocity_encoder = VelocityEncoder(self.alt_vel, self.input_steps, self.n_objs, self.coord_units,
                                                 self.device)
         self.rollout_cell = self.cell(self.coord_units // 2, self.coord_units // 2)
+        if learn_sigma:
+            # fp32 on purpose: the base learning rate and the "decoder" group,
+            # not the fp64 physics buffer's (flat.py)
+            self.decoder_sigma_u = pnn.Parameter(torch.tensor(float(u0), dtype=torch.float32))
+            self.learn_sigma = True
+        object.__setattr__(self, "_sigma_dev", None)
         # the standalone U-Net / encoder forwards run on this model's engine
         for mod in (self.encoder, self.encoder.shallow_unet, self.encoder.unet):
             object.__setattr__(mod, "_paig_owner", weakref.ref(self))
@@ -325,11 +341,13 @@ class PhysicsNet(BaseNetTorch):
         dead = "encoder.unet." if self.conv_input_shape[1] < 40 else "encoder.shallow_unet."
         names = []
         for n, p in self.named_parameters():
-            if n.startswith(dead) or n.startswith("rollout_cell."):
+            if n.startswith(dead) or n.startswith("rollout_cell.") or n == "decoder_sigma_u":
                 continue
             names.append(n)
         names = ([n for n in names if n.startswith(self.EARLY_GRADS)] +
                  [n for n in names if not n.startswith(self.EARLY_GRADS)])
+        if self.learn_sigma:   # the last slot of the fp32 buffer's late part: every other offset as without it
+            names.append("decoder_sigma_u")
         if self.cell_type == "spring_ode_cell":
             names += ["rollout_cell.k", "rollout_cell.equil"]
         elif self.cell_type == "gravity_ode_cell":
@@ -401,10 +419,32 @@ class PhysicsNet(BaseNetTorch):
 
     SIGMA_RANGE = (0.5, 2.0)
 
+    def __setattr__(self, name, value):
+        if name == "log_sig" and self.__dict__.get("learn_sigma"):
+            raise AttributeError("log_sig is fixed in learnable mode: set the parameter decoder_sigma_u "
+                                 "(sigma = exp(ln 2 tanh(u)))")
+        super().__setattr__(name, value)
+
+    def sigma_buffer(self):
+        """Learnable mode: the one-double device buffer the decoders read
+        sigma from (paig_sigma_from_u writes it at the start of every forward).
+        Persistent, so a captured step keeps its address."""
+        dev = self.decoder_sigma_u.device
+        if self._sigma_dev is None or self._sigma_dev.device != dev:
+            object.__setattr__(self, "_sigma_dev", torch.ones(1, device=dev, dtype=torch.float64))
+        return self._sigma_dev
+
     def decoder_sigma(self):
         """The decoders' attention-window scale of this forward, as the
         reference forms it (physics_models.py:160): np.exp(np.log(log_sig)), a
-        float64.  The HIP decoders serve [0.5, 2]."""
+        float64.  The HIP decoders serve [0.5, 2].
+
+        Learnable mode: exp(ln 2 tanh(u)) of the current decoder_sigma_u, in
+        fp64 as the device forms it.  One device read: it SYNCHRONISES, so
+        call it at log steps only (the step itself never does)."""
+        if self.learn_sigma:
+            u = np.float64(np.float32(self.decoder_sigma_u.detach().item()))
+            return float(np.exp(np.log(2.0) * np.tanh(u)))
         with np.errstate(all="ignore"):
             sigma = float(np.exp(np.log(np.float64(self.log_sig))))
         lo, hi = self.SIGMA_RANGE
@@ -522,8 +562,9 @@ class PhysicsNet(BaseNetTorch):
         dev = pos.device
         cont = torch.empty(K + 1, N, 3, H, H, device=dev)
         masks = torch.empty(K + 1, N, 3, H, H, device=dev)
-        lib().paig_decoder_parts_sigma(ptr(pos), inner, ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"]),
-                                       ptr(cont), ptr(masks), N, K, H // 2, H, sigma, stream_handle(dev))
+        parts = lib().paig_decoder_parts_sigma_dev if torch.is_tensor(sigma) else lib().paig_decoder_parts_sigma
+        parts(ptr(pos), inner, ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"]), ptr(cont), ptr(masks), N, K,
+              H // 2, H, ptr(sigma) if torch.is_tensor(sigma) else sigma, stream_handle(dev))
         res = ([cont[k] for k in range(K + 1)], tuple(masks[k] for k in range(K + 1)))
         object.__setattr__(self, "_parts_cache", (self._parts, res))
         return res

@@ -110,6 +110,9 @@ def build_parser():
                    help="1: render a missing --synthetic dataset on the GPU and keep it there (no npz written)")
     p.add_argument("--sigma", type=float, default=1.0,
                    help="decoder attention-window scale (PhysicsNet.log_sig), in [0.5, 2]: 2 halves the window")
+    p.add_argument("--learn_sigma", action="store_true",
+                   help="train the decoder attention-window scale on the device (sigma = exp(ln 2 tanh(u)), one "
+                        "extra parameter decoder_sigma_u); --sigma is its start value, strictly inside (0.5, 2)")
     p.add_argument("--clip_grad_norm", type=float, default=0.0,
                    help="clip the global gradient norm to this value before the update (0: off)")
     p.add_argument("--physics_lr_mult", type=float, default=1.0,
@@ -178,7 +181,7 @@ def main(argv=None):
             torch.manual_seed(args.seed)
         net = Model(args.task, args.recurrent_units, args.lstm_layers, cell_type, sl, input_steps, pred_steps,
                     args.autoencoder_loss, args.alt_vel, args.color, input_size, args.encoder_type,
-                    args.decoder_type, device=device, sigma=args.sigma)
+                    args.decoder_type, device=device, sigma=args.sigma, learn_sigma=args.learn_sigma)
         net.loss_mode = args.loss_mode
         net.conv_math = args.conv_math or ("bf16" if args.dtype == "bf16" else "split")
         net.to(net.device)
