@@ -31,7 +31,7 @@ extern "C" {
 /* Version of this interface: bumped whenever an entry point's argument list
  * or a data layout it exchanges changes (the Python binding refuses a library
  * of another version). */
-#define PAIG_ABI_VERSION 11
+#define PAIG_ABI_VERSION 12
 const char* paig_last_error(void);
 int paig_abi_version(void);
 /* f16 range guard of the split-precision path.  Activations and gradients
@@ -482,7 +482,8 @@ int paig_localiser_bwd(const float* dpos, const float* x1, const float* h1, cons
  * packed input gradient and d pos0 added into dpos [B][Te][2K]) writes the
  * MLP's [W0|b0|W2|b2|W4|b4] gradient to dmlp (overwritten) and the physics
  * parameters' to gparam0/1 (fp64; workspace paig_velmlp_rollout_bwd_workspace
- * bytes).  alt_vel (the linear velocity encoder) is not covered. */
+ * bytes).  alt_vel (the linear velocity encoder) is not covered.  cell: any
+ * kind of paig_rollout_fwd (D = 2K), the 2-D kinds 3 and 4 included. */
 int paig_velmlp_rollout_fwd(int cell, const float* pos, int B, int Te, int K, int S, const float* W0, const float* b0,
                             const float* W2, const float* b2, const float* W4, const float* b4, float* X, float* h1,
                             float* h2, float* vel0, const float* dt, const double* p0, const double* p1, float* pvs,
@@ -501,7 +502,11 @@ int paig_vel_unpack_add(const float* dX, const float* dpos0, float* dpos, int B,
 
 /* ---- physics rollout: all R steps x 5 substeps (cells.py:31-51, 60-83,
  *      96-106; loop physics_models.py:231-239).  cell 0 spring, 1 bouncing,
- *      2 gravity.  dt/p0/p1 are device 0-dim params (p0,p1 = k,equil | g,m). */
+ *      2 gravity (the reference's cells, split-size-1 quirk included); 3 spring
+ *      2-D, 4 bouncing 2-D (the same cells with split size 2: objects (x0, y0)
+ *      and (x1, y1), a vector spring / four walls; D = 4).
+ *      dt/p0/p1 are device 0-dim params (p0,p1 = k,equil | g,m; cells 1 and 4
+ *      take none).  A (cell, D) pair with no kernel is PAIG_E_UNSUPPORTED. */
 int paig_rollout_fwd(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
                      const double* p0, const double* p1, float* pvs, int B, int D, int R, void* stream);
 int paig_rollout_bwd_blocks(int B);

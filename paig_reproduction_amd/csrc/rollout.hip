@@ -8,6 +8,9 @@
 //   bouncing_ode_cell.forward :60-83  (same split-size-1 quirk, hard walls 0/32)
 //   gravity_ode_cell.forward  :96-106 (3 bodies, A = exp(g) exp(2m); computed
 //                                      per call here, quirk Q4)
+// Opt-in, beside them: the spring and bouncing cells with split size 2 (two
+// objects in the plane joined by a vector spring; two balls and four walls),
+// kinds 3 and 4, on the generic serial adjoint.
 // The rollout loop itself is PhysicsNet.conv_feedforward :231-239.
 //
 // The reference issues ~100 tiny elementwise ops per step; here each thread
@@ -82,6 +85,8 @@ rollout_bwd_k(const float* __restrict__ pvs, const float* __restrict__ dpos_roll
         }
         if (CELL == CELL_SPRING) spring_sub(P, p, v);
         else if (CELL == CELL_BOUNCE) bounce_sub(P, p, v, &fl[s]);
+        else if (CELL == CELL_SPRING2D) spring2d_sub(P, p, v);
+        else if (CELL == CELL_BOUNCE2D) bounce2d_sub(P, p, v, &fl[s]);
         else grav_sub(P, p, v);
       }
       float s0 = 0.f, s1 = 0.f;   // this step's parameter adjoints
@@ -89,6 +94,8 @@ rollout_bwd_k(const float* __restrict__ pvs, const float* __restrict__ dpos_roll
       for (int s = 4; s >= 0; --s) {
         if (CELL == CELL_SPRING) spring_sub_bwd(P, ps[s], vs[s], gp, gv, s0, s1);
         else if (CELL == CELL_BOUNCE) bounce_sub_bwd(P, fl[s], gp, gv);
+        else if (CELL == CELL_SPRING2D) spring2d_sub_bwd(P, ps[s], gp, gv, s0, s1);
+        else if (CELL == CELL_BOUNCE2D) bounce2d_sub_bwd(P, fl[s], gp, gv);
         else grav_sub_bwd(P, ps[s], gp, gv, s0);
       }
       g0 += (double)s0;
@@ -298,6 +305,7 @@ rollout_bwd_spring_scan_k(const float* __restrict__ pvs, const float* __restrict
 __global__ void rollout_param_final_k(const double* __restrict__ part, int nblk, int cell, PhysPtr Q,
                                       double* __restrict__ g0, double* __restrict__ g1, int accumulate) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (cell == CELL_SPRING2D) cell = CELL_SPRING;   // the same parameters (k, equil)
   const double ek = cell == CELL_SPRING ? exp(*Q.p0) : 0.0;
   const double tee = cell == CELL_SPRING ? 2.0 * exp(*Q.p1) : 0.0;
   const double negA = cell == CELL_GRAVITY ? -(exp(*Q.p0) * exp(2.0 * *Q.p1)) : 0.0;
@@ -339,18 +347,21 @@ static int launch_bwd(const float* pvs, const float* dpr, const float* dpvs, Phy
 
 extern "C" {
 
-// cell: 0 spring (params k, equil), 1 bouncing (none), 2 gravity (params g, m).
+// cell: 0 spring (params k, equil), 1 bouncing (none), 2 gravity (params g, m),
+// 3 spring 2-D (k, equil), 4 bouncing 2-D (none).
 // dt: 0-dim fp32 device param; p0/p1: 0-dim fp64 device params (k, equil)
-// or (g, m); null for bouncing.  Nothing is read back to the host.
+// or (g, m); null for the bouncing cells.  Nothing is read back to the host.
 int paig_rollout_fwd(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
                      const double* p0, const double* p1, float* pvs, int B, int D, int R, void* stream) {
   if (B <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  PAIG_REQUIRE(cell == CELL_BOUNCE || (p0 && p1), "rollout: physics params required");
+  PAIG_REQUIRE(cell == CELL_BOUNCE || cell == CELL_BOUNCE2D || (p0 && p1), "rollout: physics params required");
   PhysPtr P{dt, p0, p1};
   if (cell == CELL_SPRING && D == 4) return launch_fwd<4, CELL_SPRING>(pos0, pos0_ld, vel0, P, pvs, B, R, st);
   if (cell == CELL_BOUNCE && D == 4) return launch_fwd<4, CELL_BOUNCE>(pos0, pos0_ld, vel0, P, pvs, B, R, st);
   if (cell == CELL_GRAVITY && D == 6) return launch_fwd<6, CELL_GRAVITY>(pos0, pos0_ld, vel0, P, pvs, B, R, st);
+  if (cell == CELL_SPRING2D && D == 4) return launch_fwd<4, CELL_SPRING2D>(pos0, pos0_ld, vel0, P, pvs, B, R, st);
+  if (cell == CELL_BOUNCE2D && D == 4) return launch_fwd<4, CELL_BOUNCE2D>(pos0, pos0_ld, vel0, P, pvs, B, R, st);
   paig_set_error("rollout: unsupported cell %d with D=%d", cell, D);
   return PAIG_E_UNSUPPORTED;
 }
@@ -364,7 +375,7 @@ int paig_rollout_bwd(int cell, const float* pvs, const float* dpos_roll, const f
                      double* gparam1, int accumulate, int B, int D, int R, void* stream) {
   if (B <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  PAIG_REQUIRE(cell == CELL_BOUNCE || (p0 && p1), "rollout: physics params required");
+  PAIG_REQUIRE(cell == CELL_BOUNCE || cell == CELL_BOUNCE2D || (p0 && p1), "rollout: physics params required");
   PhysPtr P{dt, p0, p1};
   int rc, nblk = cdiv(B, 64);
   if (cell == CELL_SPRING && D == 4 && R <= 64) {   // one wave per sequence, a lane per step
@@ -376,12 +387,15 @@ int paig_rollout_bwd(int cell, const float* pvs, const float* dpos_roll, const f
   } else if (cell == CELL_SPRING && D == 4) rc = launch_bwd<4, CELL_SPRING>(pvs, dpos_roll, dpvs, P, dpos0, dvel0, part, B, R, st);
   else if (cell == CELL_BOUNCE && D == 4) rc = launch_bwd<4, CELL_BOUNCE>(pvs, dpos_roll, dpvs, P, dpos0, dvel0, part, B, R, st);
   else if (cell == CELL_GRAVITY && D == 6) rc = launch_bwd<6, CELL_GRAVITY>(pvs, dpos_roll, dpvs, P, dpos0, dvel0, part, B, R, st);
+  // the 2-D cells: the serial adjoint at every R (the spring's step maps are 8 x 8: no scan form)
+  else if (cell == CELL_SPRING2D && D == 4) rc = launch_bwd<4, CELL_SPRING2D>(pvs, dpos_roll, dpvs, P, dpos0, dvel0, part, B, R, st);
+  else if (cell == CELL_BOUNCE2D && D == 4) rc = launch_bwd<4, CELL_BOUNCE2D>(pvs, dpos_roll, dpvs, P, dpos0, dvel0, part, B, R, st);
   else {
     paig_set_error("rollout: unsupported cell %d with D=%d", cell, D);
     return PAIG_E_UNSUPPORTED;
   }
   if (rc) return rc;
-  if (cell != CELL_BOUNCE) {
+  if (cell != CELL_BOUNCE && cell != CELL_BOUNCE2D) {
     hipLaunchKernelGGL(rollout_param_final_k, dim3(1), dim3(64), 0, st, part, nblk, cell, P, gparam0, gparam1,
                        accumulate);
     PAIG_CHECK_LAUNCH();

@@ -4,7 +4,9 @@
 // Included inside each translation unit's anonymous namespace.
 #pragma once
 
-enum { CELL_SPRING = 0, CELL_BOUNCE = 1, CELL_GRAVITY = 2 };
+// CELL_SPRING2D / CELL_BOUNCE2D: the same cells with split size 2 (opt-in, not
+// the reference's behaviour): objects (x0, y0) and (x1, y1) in the plane
+enum { CELL_SPRING = 0, CELL_BOUNCE = 1, CELL_GRAVITY = 2, CELL_SPRING2D = 3, CELL_BOUNCE2D = 4 };
 
 struct Phys {
   float h;     // dt / 5 (fp32, as torch computes self.dt / 5)
@@ -68,6 +70,64 @@ __device__ __forceinline__ void spring_sub_bwd(const Phys& P, const float* p, co
   gp[1] -= gd;
 }
 
+// ------------------------------------------------------------- spring 2-D ----
+// spring_ode_cell.forward with split size 2: p = (x0, y0, x1, y1), a vector
+// spring between the two objects.  The reference's operations in its order,
+// each rounded on its own: n = sqrt(|sum((p0 - p1)^2, -1)|) keeps the two
+// squares and their sum as three operations (no FMA contraction here).
+__device__ __forceinline__ void spring2d_sub(const Phys& P, float* p, float* v) {
+#pragma clang fp contract(off)
+  const float dx = p[0] - p[2], dy = p[1] - p[3];
+  const float sq = dx * dx + dy * dy;
+  const float n = sqrtf(fabsf(sq));
+  const float den = n + 1e-4f;
+  const float e = P.ek * (n - P.tee);
+  const float Fx = e * (dx / den), Fy = e * (dy / den);
+  v[0] = v[0] - P.h * Fx;
+  v[1] = v[1] - P.h * Fy;
+  v[2] = v[2] + P.h * Fx;
+  v[3] = v[3] + P.h * Fy;
+  for (int j = 0; j < 4; ++j) p[j] = p[j] + P.h * v[j];
+}
+
+// adjoint of one 2-D spring substep given its INPUT positions p (aten's
+// rules as in spring_sub_bwd: sqrt' = g / (2 sqrt), abs' = sgn; v_rcp_f32 for
+// the divisions; parameter adjoints in fp32 within a step).  Not finite at
+// n = 0, as the reference's arithmetic: there d / (n + 1e-4) has a 1e4 slope
+// and a step multiplies the separation's adjoint by ~865 per substep.
+__device__ __forceinline__ void spring2d_sub_bwd(const Phys& P, const float* p, float* gp, float* gv, float& gek,
+                                                 float& gtee) {
+  const float dx = p[0] - p[2], dy = p[1] - p[3];
+  const float sq = dx * dx + dy * dy;
+  const float n = sqrtf(fabsf(sq));
+  const float rden = __builtin_amdgcn_rcpf(n + 1e-4f);
+  const float dirx = dx * rden, diry = dy * rden;
+  const float nm = n - P.tee;
+  // p' = p + h v'
+  for (int j = 0; j < 4; ++j) gv[j] += P.h * gp[j];
+  // v0' = v0 - h F ; v1' = v1 + h F
+  const float gFx = P.h * gv[2] - P.h * gv[0], gFy = P.h * gv[3] - P.h * gv[1];
+  // F = (ek * (n - tee)) * dir
+  const float ge = gFx * dirx + gFy * diry;
+  gek += ge * nm;
+  const float gnm = ge * P.ek;
+  gtee -= gnm;
+  const float e = P.ek * nm;
+  const float gdirx = gFx * e, gdiry = gFy * e;
+  // dir = d / (n + 1e-4)
+  float gdx = gdirx * rden, gdy = gdiry * rden;
+  const float gn = gnm - (gdirx * dx + gdiry * dy) * (rden * rden);
+  // n = sqrt(|dx dx + dy dy|)
+  const float sg = sq > 0.f ? 1.f : (sq < 0.f ? -1.f : 0.f);
+  const float gsq = gn * __builtin_amdgcn_rcpf(2.f * n) * sg;
+  gdx += gsq * 2.f * dx;
+  gdy += gsq * 2.f * dy;
+  gp[0] += gdx;
+  gp[1] += gdy;
+  gp[2] -= gdx;
+  gp[3] -= gdy;
+}
+
 // -------------------------------------------------------------- bouncing ----
 __device__ __forceinline__ void bounce_sub(const Phys& P, float* p, float* v, unsigned* fl) {
   p[0] = p[0] + P.h * v[0];
@@ -96,6 +156,38 @@ __device__ __forceinline__ void bounce_sub_bwd(const Phys& P, unsigned fl, float
   }
   gv[0] += P.h * gp[0];
   gv[1] += P.h * gp[1];
+}
+
+// ----------------------------------------------------------- bouncing 2-D ----
+// bouncing_ode_cell.forward with split size 2: the same substep on all four
+// coordinates (two balls, four walls); flags a, b, c of coordinate j in bits
+// 3j .. 3j+2 (12 bits)
+__device__ __forceinline__ void bounce2d_sub(const Phys& P, float* p, float* v, unsigned* fl) {
+#pragma clang fp contract(off)
+  unsigned f = 0;
+  for (int j = 0; j < 4; ++j) {
+    p[j] = p[j] + P.h * v[j];
+    const bool a = p[j] + 2.f > 32.f;
+    if (a) v[j] = -v[j];
+    const bool b = 0.f > p[j] - 2.f;
+    if (b) v[j] = -v[j];
+    if (a) p[j] = 32.f - (p[j] + 2.f - 32.f) - 2.f;
+    const bool c = 0.f > p[j] - 2.f;
+    if (c) p[j] = -(p[j] - 2.f) + 2.f;
+    f |= ((a ? 1u : 0u) | (b ? 2u : 0u) | (c ? 4u : 0u)) << (3 * j);
+  }
+  *fl = f;
+}
+
+__device__ __forceinline__ void bounce2d_sub_bwd(const Phys& P, unsigned fl, float* gp, float* gv) {
+  for (int j = 0; j < 4; ++j) {   // (the coordinates are independent)
+    const unsigned f = fl >> (3 * j);
+    if (f & 4u) gp[j] = -gp[j];
+    if (f & 1u) gp[j] = -gp[j];
+    if (f & 2u) gv[j] = -gv[j];
+    if (f & 1u) gv[j] = -gv[j];
+    gv[j] += P.h * gp[j];
+  }
 }
 
 // --------------------------------------------------------------- gravity ----
@@ -185,8 +277,8 @@ __device__ __forceinline__ void grav_sub_bwd(const Phys& P, const float* p, floa
 
 struct PhysPtr {
   const float* dt;   // 0-dim fp32 parameter (requires_grad=False)
-  const double* p0;  // k (spring) | g (gravity) | null
-  const double* p1;  // equil (spring) | m (gravity) | null
+  const double* p0;  // k (spring, spring 2-D) | g (gravity) | null
+  const double* p1;  // equil (spring, spring 2-D) | m (gravity) | null
 };
 
 template <int CELL>
@@ -196,7 +288,7 @@ __device__ __forceinline__ Phys load_phys(const PhysPtr& q) {
   P.ek = 0.f;
   P.tee = 0.f;
   P.negA = 0.f;
-  if (CELL == CELL_SPRING) {
+  if (CELL == CELL_SPRING || CELL == CELL_SPRING2D) {
     P.ek = (float)exp(*q.p0);
     P.tee = (float)(2.0 * exp(*q.p1));
   } else if (CELL == CELL_GRAVITY) {
@@ -210,6 +302,8 @@ __device__ __forceinline__ void step_fwd(const Phys& P, float* p, float* v) {
   for (int s = 0; s < 5; ++s) {
     if (CELL == CELL_SPRING) spring_sub(P, p, v);
     else if (CELL == CELL_BOUNCE) { unsigned fl; bounce_sub(P, p, v, &fl); }
+    else if (CELL == CELL_SPRING2D) spring2d_sub(P, p, v);
+    else if (CELL == CELL_BOUNCE2D) { unsigned fl; bounce2d_sub(P, p, v, &fl); }
     else grav_sub(P, p, v);
   }
 }

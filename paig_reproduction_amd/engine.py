@@ -115,7 +115,9 @@ class Layout:
         else:
             self.F = frames
         self.alt_vel = model.alt_vel
-        self.cell = {"spring_ode_cell": 0, "bouncing_ode_cell": 1, "gravity_ode_cell": 2}[model.cell_type]
+        # paig_rollout_fwd's cell kinds (3, 4: the opt-in split-size-2 cells)
+        self.cell = {"spring_ode_cell": 0, "bouncing_ode_cell": 1, "gravity_ode_cell": 2, "spring2d_ode_cell": 3,
+                     "bouncing2d_ode_cell": 4}[model.cell_type]
         self.unet = self.H >= 40 if net is None else net == "unet"
         L = lib()
         self.net = 1 if self.unet else 0   # paig_unet_*: 0 ShallowUNet(hidden 8), 1 UNet(hidden 16)
@@ -767,7 +769,7 @@ class Engine:
     def cell_params(self, lay):
         m = self.model
         dt = m.rollout_cell.dt
-        if lay.cell == 0:
+        if lay.cell in (0, 3):
             return dt, m.rollout_cell.k, m.rollout_cell.equil
         if lay.cell == 2:
             return dt, m.rollout_cell.g, m.rollout_cell.m
@@ -872,7 +874,7 @@ class Engine:
         # ---- rollout adjoint -> d pos0, d vel0, physics params; velocity encoder backward
         prm = self.cell_params(lay)
         gk = gq = None
-        if lay.cell == 0:
+        if lay.cell in (0, 3):
             gk, gq = self.g("rollout_cell.k"), self.g("rollout_cell.equil")
         elif lay.cell == 2:
             gk = self.g("rollout_cell.g")

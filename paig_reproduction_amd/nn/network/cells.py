@@ -7,7 +7,10 @@ The integrators themselves run fused over all rollout steps in the HIP kernel
 ``paig_rollout_fwd/bwd`` (csrc/rollout.hip), which restates
 spring (:31-51), bouncing (:60-83) and gravity (:96-106) exactly, including
 the split-size-1 quirk Q3.  Gravity recomputes A = exp(g) exp(2m) per step
-(the reference computes it once in __init__, Q4)."""
+(the reference computes it once in __init__, Q4).
+
+spring2d_ode_cell / bouncing2d_ode_cell (rollout kinds 3 / 4) are the opt-in
+fix of Q3: the same cells with split size 2, two objects in the plane."""
 import numpy as np
 import torch
 import torch.nn as tnn
@@ -54,6 +57,22 @@ class bouncing_ode_cell(ode_cell):
     def __init__(self, input_size, hidden_size):
         super().__init__(input_size, hidden_size)
         self.dt = tnn.Parameter(torch.tensor(0.3), requires_grad=False)
+
+
+class spring2d_ode_cell(spring_ode_cell):
+    """Opt-in (not the reference's behaviour): spring_ode_cell with split
+    size 2.  The two objects (x0, y0) and (x1, y1) are joined by a vector
+    spring, F = exp(k) (|d| - 2 exp(equil)) d / |d| with d = p0 - p1: the
+    physics nn/datasets/synth.py renders.  Same parameters, creation order,
+    state_dict and init RNG stream as spring_ode_cell."""
+    KIND = 3
+
+
+class bouncing2d_ode_cell(bouncing_ode_cell):
+    """Opt-in (not the reference's behaviour): bouncing_ode_cell with split
+    size 2.  All four coordinates move and bounce off the walls 0 and 32
+    (radius 2); no ball-to-ball collisions, as in the reference."""
+    KIND = 4
 
 
 class gravity_ode_cell(ode_cell):

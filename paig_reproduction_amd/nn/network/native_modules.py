@@ -106,7 +106,7 @@ class _Cell(torch.autograd.Function):
         p0, p1 = _cell_params(cell)
         L.paig_rollout_bwd(cell.KIND, ptr(pvs), ptr(dpos_roll), ptr(dpvs), ptr(cell.dt), ptr(p0), ptr(p1), ptr(dpos0),
                            ptr(dvel0), ptr(part), ptr(gq), ptr(gq) + 8, 0, B, D, 1, stream_handle(dev))
-        if cell.KIND == 0:
+        if cell.KIND in (0, 3):
             deposit_grad(cell.k, gq[0])
             deposit_grad(cell.equil, gq[1])
         elif cell.KIND == 2:
@@ -116,7 +116,7 @@ class _Cell(torch.autograd.Function):
 
 
 def _cell_params(cell):
-    if cell.KIND == 0:
+    if cell.KIND in (0, 3):   # spring, spring 2-D
         return cell.k, cell.equil
     if cell.KIND == 2:
         return cell.g, cell.m

@@ -24,7 +24,8 @@ from paig_reproduction_amd.engine import Engine, LossAdjoints, live_steps, mater
 from paig_reproduction_amd.flat import FlatParams
 from paig_reproduction_amd.nn.network.base import OPTIMIZERS, BaseNetTorch
 from paig_reproduction_amd.nn.network.blocks import ConvolutionalEncoder, VelocityEncoder, VariableFromNetwork
-from paig_reproduction_amd.nn.network.cells import bouncing_ode_cell, spring_ode_cell, gravity_ode_cell
+from paig_reproduction_amd.nn.network.cells import (bouncing_ode_cell, spring_ode_cell, gravity_ode_cell,
+                                                    spring2d_ode_cell, bouncing2d_ode_cell)
 
 logger = logging.getLogger("tf")
 
@@ -32,6 +33,9 @@ CELLS = {
     "bouncing_ode_cell": bouncing_ode_cell,
     "spring_ode_cell": spring_ode_cell,
     "gravity_ode_cell": gravity_ode_cell,
+    # opt-in (--physics_2d): the spring / bouncing cells with split size 2
+    "spring2d_ode_cell": spring2d_ode_cell,
+    "bouncing2d_ode_cell": bouncing2d_ode_cell,
     "lstm": pnn.LSTMCell,
 }
 
@@ -348,7 +352,7 @@ class PhysicsNet(BaseNetTorch):
                  [n for n in names if not n.startswith(self.EARLY_GRADS)])
         if self.learn_sigma:   # the last slot of the fp32 buffer's late part: every other offset as without it
             names.append("decoder_sigma_u")
-        if self.cell_type == "spring_ode_cell":
+        if self.cell_type in ("spring_ode_cell", "spring2d_ode_cell"):
             names += ["rollout_cell.k", "rollout_cell.equil"]
         elif self.cell_type == "gravity_ode_cell":
             names += ["rollout_cell.g"]

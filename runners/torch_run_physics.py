@@ -20,6 +20,11 @@ Additive flags only:
         base_lr * M (default 1).
   --log_grad_norms               total and per-group gradient norms on the train lines,
         a warning when a group's gradients are exactly zero.
+  --physics_2d                   two objects in the plane: spring_color, spring_color_half,
+        mnist_spring_color and bouncing_balls roll out with spring2d_ode_cell / bouncing2d_ode_cell
+        (the cells with split size 2: a vector spring between (x0, y0) and (x1, y1); four walls)
+        instead of the reference's split-size-1 cells (quirk Q3).  Off by default; the
+        state_dict is the same, so checkpoints move between the two.  An error for 3bp_color.
   --synthetic_device {0,1}       1: with --synthetic N and the task's npz missing,
         render the data on the GPU instead (nn/datasets/synth_device.py: HIP
         integrators + rasteriser) and keep it in HBM; no npz is written.  Same
@@ -119,7 +124,26 @@ def build_parser():
                    help="learning rate of the physics parameters (rollout_cell.*), as a multiple of --base_lr")
     p.add_argument("--log_grad_norms", action="store_true",
                    help="log the total and per-group gradient norms on the train lines")
+    p.add_argument("--physics_2d", action="store_true",
+                   help="two objects in the plane: the task's spring / bouncing cell with split size 2 (a vector "
+                        "spring, four walls) instead of the reference's split-size-1 cell; not for 3bp_color")
     return p
+
+
+# --physics_2d: the task's preset cell -> its split-size-2 class
+CELLS_2D = {"spring_ode_cell": "spring2d_ode_cell", "bouncing_ode_cell": "bouncing2d_ode_cell"}
+
+
+def task_cell(args):
+    """The rollout cell of args.task: TASKS' preset, or under --physics_2d its
+    2-D class (an error for a task whose cell has none)."""
+    cell = TASKS[args.task][2]
+    if not args.physics_2d:
+        return cell
+    if cell not in CELLS_2D:
+        raise SystemExit(f"--physics_2d: task {args.task} ({cell}) has no 2-D cell; it applies to " +
+                         ", ".join(t for t, v in TASKS.items() if v[2] in CELLS_2D))
+    return CELLS_2D[cell]
 
 
 def dataset_path(args, rel, seq_len):
@@ -163,6 +187,7 @@ def main(argv=None):
     Model = classes_in_module(physics_models)[args.model]
     data_file, test_data_file, cell_type, seq_len, test_seq_len, input_steps, pred_steps, input_size = \
         TASKS[args.task]
+    cell_type = task_cell(args)   # the training model and the test-time model alike
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
