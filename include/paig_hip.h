@@ -741,6 +741,47 @@ int paig_synth_integrate(int phys, const double* p0, const double* v0, long long
  * three channels (byte = uint8(clip(max(bg, cover), 0, 1) * 255)). */
 int paig_synth_raster(const double* pos, const long long* rows, long long n, int T, int K, int size, double radius,
                       const float* bg, unsigned char* out, void* stream);
+/* paig_synth_raster_ex: the same kernel with rows (required) produced on the
+ * device and never seen by the host: sequence i is left untouched when
+ * rows[i] is outside [0, m) (m = trajectories in pos; -1 is the "no row"
+ * value of paig_synth_compact). */
+int paig_synth_raster_ex(const double* pos, const long long* rows, long long m, long long n, int T, int K, int size,
+                         double radius, const float* bg, unsigned char* out, void* stream);
+/* paig_synth_draw: m candidate initial states p0 / v0 (fp64 [m, K, 2]) drawn on
+ * the device, one lane each, from the distributions of
+ * synth_device.initial_conditions (radius = the bound radius, c0 / c1 as for
+ * paig_synth_integrate, vmax the speed scale, half != 0 the left-half centre of
+ * mass of spring_color_half).  Uniforms are Philox4x32-10 blocks with key
+ * (seed, stream_id) and counter (candidate low word, candidate high word,
+ * round, draw slot), seed / stream_id / round each in [0, 2^32); a double is
+ * ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53 (numpy's rule), u[2 s] from words
+ * (0, 1) and u[2 s + 1] from words (2, 3) of slot s.  Use of u0 .. u7:
+ *   spring   u0 u1 centre of mass (x, y); u2 pair angle; u3 + 0.5 pair distance
+ *            in units of c1; u4 u5 velocity angles of objects 0, 1; u6 u7 their
+ *            speeds in units of vmax
+ *   bounce   u0 u1 / u2 u3 positions of objects 0 / 1; u4 u5 velocity angles;
+ *            0.5 + 0.5 u6, 0.5 + 0.5 u7 speeds in units of vmax
+ *   gravity  u0 angle of object 0 (the others at + 2 pi / 3, + 4 pi / 3);
+ *            4 + 4 u1 the orbit radius (slot 0 only)
+ * A candidate depends on (seed, stream_id, round, its index) only, not on m.
+ * u (nullable): fp64 [m, 8] receives the uniforms (unused ones 0). */
+int paig_synth_draw(int phys, long long seed, long long stream_id, long long round, long long m, int K, int half,
+                    double size, double radius, double c0, double c1, double vmax, double* p0, double* v0, double* u,
+                    void* stream);
+/* paig_synth_background: bg fp32 [n, size, size] = clip(U - 0.2, 0, 1), the
+ * mnist_spring_color background, U = (word >> 8) * 2^-24; pixels 4 q .. 4 q + 3
+ * of the flat array are the words of the Philox block with counter (q low, q
+ * high, round, 0x6267) and the key of paig_synth_draw. */
+int paig_synth_background(long long seed, long long stream_id, long long round, long long n, int size, float* bg,
+                          void* stream);
+/* paig_synth_compact: rows[i] (int64 [n]) = index of the i-th nonzero flag of
+ * valid (int32 [m], m < 2^31) in candidate order for i < min(accepted, n), -1
+ * beyond; count (int32 [2]) = {min(accepted, n), accepted}.  One block walks
+ * the flags in order (wave ballot, popcount, running prefix; no atomics), so
+ * the result is deterministic.  totals (nullable, int64 [3]) accumulates
+ * {calls, min(accepted, n), n - min(accepted, n)} over the calls of one stream. */
+int paig_synth_compact(const int* valid, long long m, long long* rows, long long n, int* count, long long* totals,
+                       void* stream);
 
 /* ---- optimizers over the flat parameter buffer (base.py:12-17, torch defaults) */
 int paig_rmsprop_f32(float* p, const float* g, float* sa, long long n, float lr, float alpha, float eps, void* stream);

@@ -158,6 +158,10 @@ SIGNATURES = {
     "paig_frame_sse_bwd": (I, [P, LL, I, LL, P, LL, I, LL, P, P, I, I, P]),
     "paig_synth_integrate": (I, [I, P, P, LL, I, I, I, F64, F64, F64, F64, F64, P, P, P]),
     "paig_synth_raster": (I, [P, P, LL, I, I, I, F64, P, P, P]),
+    "paig_synth_raster_ex": (I, [P, P, LL, LL, I, I, I, F64, P, P, P]),
+    "paig_synth_draw": (I, [I, LL, LL, LL, LL, I, I, F64, F64, F64, F64, F64, P, P, P, P]),
+    "paig_synth_background": (I, [LL, LL, LL, LL, I, P, P]),
+    "paig_synth_compact": (I, [P, LL, P, LL, P, P, P]),
     "paig_rmsprop_f32": (I, [P, P, P, LL, F32, F32, F32, P]),
     "paig_rmsprop_f64": (I, [P, P, P, LL, F64, F64, F64, P]),
     "paig_rmsprop_mixed": (I, [P, P, P, LL, P, P, P, LL, F64, F64, F64, P]),

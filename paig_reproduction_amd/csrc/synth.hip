@@ -130,12 +130,192 @@ __device__ __forceinline__ int rim_count(int px, int py, double x, double y, dou
   return k;
 }
 
+// ---- candidates drawn on the device -----------------------------------------
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3",
+// SC'11; the Random123 constants).  key = (seed, stream id), counter =
+// (candidate low word, candidate high word, round, draw slot): every block of
+// four words is a pure function of those, so a candidate does not depend on m
+// or on the launch shape.
+struct Philox4 {
+  uint32_t w[4];
+};
+
+__host__ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                                          uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t a = (uint64_t)0xD2511F53u * c0, b = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(b >> 32) ^ c1 ^ k0, n1 = (uint32_t)b;
+    const uint32_t n2 = (uint32_t)(a >> 32) ^ c3 ^ k1, n3 = (uint32_t)a;
+    c0 = n0, c1 = n1, c2 = n2, c3 = n3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+
+// numpy's double from two 32-bit words: 53 random bits in [0, 1)
+__device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
+  return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+enum { DRAW_SLOTS = 4, DRAW_U = 2 * DRAW_SLOTS };
+
+// One lane per candidate.  Uniform u[2 s] / u[2 s + 1] come from words (0, 1)
+// / (2, 3) of draw slot s.  Their use, fixed (synth_device.initial_conditions_philox
+// is the same arithmetic, operation for operation):
+//   spring   u0 u1 centre of mass x y (half: x from the left half with the same u0);
+//            u2 pair angle, u3 pair distance factor - 0.5; u4 u5 velocity angles
+//            of objects 0 1; u6 u7 their speed factors
+//   bounce   u0 u1 position of object 0, u2 u3 of object 1; u4 u5 velocity
+//            angles; u6 u7 speed factors (0.5 + 0.5 u)
+//   gravity  u0 angle of object 0, u1 orbit radius factor (slot 0 only)
+template <int K, int PHYS>
+__global__ void __launch_bounds__(64)
+synth_draw_k(uint32_t k0, uint32_t k1, uint32_t round, long long m, int half, double size, double rb, double c0,
+             double c1, double vmax, double* __restrict__ p0, double* __restrict__ v0, double* __restrict__ udbg) {
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  constexpr int SLOTS = PHYS == PHYS_GRAVITY ? 1 : DRAW_SLOTS;
+  constexpr double PI = 3.141592653589793;
+  double u[DRAW_U];
+#pragma unroll
+  for (int s = 0; s < DRAW_SLOTS; ++s) {
+    if (s < SLOTS) {
+      const Philox4 x = philox4x32_10((uint32_t)i, (uint32_t)((unsigned long long)i >> 32), round, (uint32_t)s, k0, k1);
+      u[2 * s] = u53(x.w[0], x.w[1]);
+      u[2 * s + 1] = u53(x.w[2], x.w[3]);
+    } else {
+      u[2 * s] = 0.0;
+      u[2 * s + 1] = 0.0;
+    }
+  }
+  if (udbg) {
+#pragma unroll
+    for (int s = 0; s < DRAW_U; ++s) udbg[i * DRAW_U + s] = u[s];
+  }
+  double p[K][2], v[K][2];
+  if (PHYS == PHYS_SPRING) {
+    const double lo = rb + c1, hi = size - (rb + c1);
+    const double cx = half ? lo + (size / 2.0 - lo) * u[0] : lo + (hi - lo) * u[0];
+    const double cy = lo + (hi - lo) * u[1];
+    const double ang = u[2] * 2.0 * PI, r = u[3] + 0.5;
+    const double ox = cos(ang) * c1 * r, oy = sin(ang) * c1 * r;
+    p[0][0] = ox + cx;
+    p[0][1] = oy + cy;
+    p[1][0] = -ox + cx;
+    p[1][1] = -oy + cy;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const double a = u[4 + j] * 2.0 * PI;
+      v[j][0] = cos(a) * vmax * u[6 + j];
+      v[j][1] = sin(a) * vmax * u[6 + j];
+    }
+  } else if (PHYS == PHYS_BOUNCE) {
+    const double span = size - 2.0 * rb;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      p[j][0] = rb + span * u[2 * j];
+      p[j][1] = rb + span * u[2 * j + 1];
+      const double a = u[4 + j] * 2.0 * PI, s = 0.5 + 0.5 * u[6 + j];
+      v[j][0] = cos(a) * vmax * s;
+      v[j][1] = sin(a) * vmax * s;
+    }
+  } else {
+    const double c = size / 2.0, a0 = u[0] * 2.0 * PI, r = 4.0 + 4.0 * u[1];
+    const double sp = sqrt(c0 / r) * 0.35;
+    const double ph[3] = {0.0, 2.0 * PI / 3.0, 4.0 * PI / 3.0};
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const double a = a0 + ph[j % 3];
+      const double cs = cos(a), sn = sin(a);
+      p[j][0] = c + r * cs;
+      p[j][1] = c + r * sn;
+      v[j][0] = -sn * sp;
+      v[j][1] = cs * sp;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    p0[(i * K + j) * 2] = p[j][0];
+    p0[(i * K + j) * 2 + 1] = p[j][1];
+    v0[(i * K + j) * 2] = v[j][0];
+    v0[(i * K + j) * 2 + 1] = v[j][1];
+  }
+}
+
+// bg [n, npix] = clip(U - 0.2, 0, 1), U = (word >> 8) 2^-24 in fp32: one lane
+// per 4 pixels = the four words of counter (quad low, quad high, round, BG_SLOT).
+enum { BG_SLOT = 0x6267 };
+
+__global__ void __launch_bounds__(256)
+synth_bg_k(uint32_t k0, uint32_t k1, uint32_t round, long long quads, float* __restrict__ bg) {
+  const long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (q >= quads) return;
+  const Philox4 x = philox4x32_10((uint32_t)q, (uint32_t)((unsigned long long)q >> 32), round, (uint32_t)BG_SLOT, k0, k1);
+  float4 o;
+  float* of = reinterpret_cast<float*>(&o);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float uf = (float)(x.w[e] >> 8) * (1.0f / 16777216.0f);
+    of[e] = fminf(fmaxf(uf - 0.2f, 0.0f), 1.0f);
+  }
+  *reinterpret_cast<float4*>(bg + 4 * q) = o;
+}
+
+// Acceptance flags -> row indices, in candidate order: one block walks the
+// flags 256 at a time; a lane's slot is the running count + the counts of the
+// waves before its own + the set lanes before it in its wave's ballot.  No
+// atomics: the order of rows is the order of the candidates, always.
+// totals (nullable, int64 [3]) accumulates {calls, min(accepted, n), n -
+// min(accepted, n)}: calls on one stream are ordered, so lane 0's plain
+// read-add-store is exact.
+__global__ void __launch_bounds__(256)
+synth_compact_k(const int* __restrict__ valid, long long m, long long* __restrict__ rows, long long n,
+                int* __restrict__ count, long long* __restrict__ totals) {
+  __shared__ int wtot[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  long long base = 0;   // accepted so far (block-uniform)
+  for (long long s = 0; s < m; s += 256) {
+    const long long i = s + tid;
+    const bool f = i < m && valid[i] != 0;
+    const unsigned long long b = __ballot(f);
+    const int pre = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) wtot[w] = __popcll(b);
+    __syncthreads();
+    int before = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c = wtot[k];
+      before += k < w ? c : 0;
+      tot += c;
+    }
+    const long long at = base + before + pre;
+    if (f && at < n) rows[at] = i;
+    base += tot;
+    __syncthreads();
+  }
+  const long long got = base < n ? base : n;
+  for (long long i = got + tid; i < n; i += 256) rows[i] = -1;
+  if (tid == 0) {
+    count[0] = (int)got;
+    count[1] = (int)base;
+    if (totals) {
+      totals[0] += 1;
+      totals[1] += got;
+      totals[2] += n - got;
+    }
+  }
+}
+
 // out [n, T, size, size, 3] uint8; grid (n * T, blocks per frame); lane q of a
-// frame renders pixels 4q .. 4q+3 (one row: size % 4 == 0).
+// frame renders pixels 4q .. 4q+3 (one row: size % 4 == 0).  m > 0 (the _ex
+// entry): rows come from the device unchecked, and a sequence whose row is
+// outside [0, m) is left as it is.
 template <int K>
 __global__ void __launch_bounds__(256)
-synth_raster_k(const double* __restrict__ pos, const long long* __restrict__ rows, int T, int size, double radius,
-               const float* __restrict__ bg, uint8_t* __restrict__ out) {
+synth_raster_k(const double* __restrict__ pos, const long long* __restrict__ rows, long long m, int T, int size,
+               double radius, const float* __restrict__ bg, uint8_t* __restrict__ out) {
   const long long f = blockIdx.x;               // frame = i * T + t (< 2^31)
   const long long i = blockIdx.x / (unsigned)T;
   const int t = (int)(f - i * T);
@@ -143,6 +323,7 @@ synth_raster_k(const double* __restrict__ pos, const long long* __restrict__ row
   const int npix = size * size;
   if (4 * q >= npix) return;
   const long long r = rows ? rows[i] : i;       // wave-uniform
+  if (m > 0 && (r < 0 || r >= m)) return;
   const double* P = pos + (r * T + t) * (K * 2);
   const int py = (4 * q) / size, px0 = (4 * q) - py * size;
 
@@ -234,15 +415,16 @@ int paig_synth_integrate(int phys, const double* p0, const double* v0, long long
   return 0;
 }
 
-int paig_synth_raster(const double* pos, const long long* rows, long long n, int T, int K, int size, double radius,
-                      const float* bg, unsigned char* out, void* stream) {
-  PAIG_REQUIRE(K == 2 || K == 3, "synth_raster: K=%d (2 or 3)", K);
-  PAIG_REQUIRE(size > 0 && size % 4 == 0 && size <= 4096, "synth_raster: size=%d (a multiple of 4, <= 4096)", size);
-  PAIG_REQUIRE(n >= 0 && T > 0 && n * T <= 0x7fffffffLL, "synth_raster: n=%lld T=%d (n * T < 2^31)", n, T);
+static int synth_raster_launch(const char* who, const double* pos, const long long* rows, long long m, long long n,
+                               int T, int K, int size, double radius, const float* bg, unsigned char* out,
+                               void* stream) {
+  PAIG_REQUIRE(K == 2 || K == 3, "%s: K=%d (2 or 3)", who, K);
+  PAIG_REQUIRE(size > 0 && size % 4 == 0 && size <= 4096, "%s: size=%d (a multiple of 4, <= 4096)", who, size);
+  PAIG_REQUIRE(n >= 0 && T > 0 && n * T <= 0x7fffffffLL, "%s: n=%lld T=%d (n * T < 2^31)", who, n, T);
   if (n == 0) return 0;
-  PAIG_REQUIRE(pos && out, "synth_raster: null operand");
-  PAIG_REQUIRE(((uintptr_t)out % 4) == 0 && ((uintptr_t)bg % 16) == 0,
-               "synth_raster: out must be 4-byte and bg 16-byte aligned");
+  PAIG_REQUIRE(pos && out, "%s: null operand", who);
+  PAIG_REQUIRE(((uintptr_t)out % 4) == 0 && ((uintptr_t)bg % 16) == 0, "%s: out must be 4-byte and bg 16-byte aligned",
+               who);
   const int quads = size * size / 4;
   // the block size (whole waves) that leaves the fewest idle lanes per frame
   int bs = 256, waste = cdiv(quads, 256) * 256 - quads;
@@ -251,12 +433,75 @@ int paig_synth_raster(const double* pos, const long long* rows, long long n, int
     if (w < waste) bs = b, waste = w;
   }
   const dim3 grid((unsigned)(n * T), (unsigned)cdiv(quads, bs)), block(bs);
-  PAIG_REQUIRE(grid.y <= 65535u, "synth_raster: size=%d too large", size);
+  PAIG_REQUIRE(grid.y <= 65535u, "%s: size=%d too large", who, size);
   hipStream_t st = (hipStream_t)stream;
   if (K == 2)
-    hipLaunchKernelGGL(synth_raster_k<2>, grid, block, 0, st, pos, rows, T, size, radius, bg, out);
+    hipLaunchKernelGGL(synth_raster_k<2>, grid, block, 0, st, pos, rows, m, T, size, radius, bg, out);
   else
-    hipLaunchKernelGGL(synth_raster_k<3>, grid, block, 0, st, pos, rows, T, size, radius, bg, out);
+    hipLaunchKernelGGL(synth_raster_k<3>, grid, block, 0, st, pos, rows, m, T, size, radius, bg, out);
+  PAIG_CHECK_LAUNCH();
+  return 0;
+}
+
+int paig_synth_raster(const double* pos, const long long* rows, long long n, int T, int K, int size, double radius,
+                      const float* bg, unsigned char* out, void* stream) {
+  return synth_raster_launch("synth_raster", pos, rows, 0, n, T, K, size, radius, bg, out, stream);
+}
+
+int paig_synth_raster_ex(const double* pos, const long long* rows, long long m, long long n, int T, int K, int size,
+                         double radius, const float* bg, unsigned char* out, void* stream) {
+  PAIG_REQUIRE(m > 0 && rows, "synth_raster_ex: m=%lld (> 0) and rows are required", m);
+  return synth_raster_launch("synth_raster_ex", pos, rows, m, n, T, K, size, radius, bg, out, stream);
+}
+
+int paig_synth_draw(int phys, long long seed, long long stream_id, long long round, long long m, int K, int half,
+                    double size, double radius, double c0, double c1, double vmax, double* p0, double* v0, double* u,
+                    void* stream) {
+  PAIG_REQUIRE(phys >= PHYS_SPRING && phys <= PHYS_GRAVITY, "synth_draw: phys=%d (0 spring, 1 bounce, 2 gravity)", phys);
+  PAIG_REQUIRE(K == (phys == PHYS_GRAVITY ? 3 : 2), "synth_draw: K=%d does not match phys=%d", K, phys);
+  PAIG_REQUIRE(seed >= 0 && seed <= 0xffffffffLL && stream_id >= 0 && stream_id <= 0xffffffffLL && round >= 0 &&
+                   round <= 0xffffffffLL,
+               "synth_draw: seed=%lld stream=%lld round=%lld (each in [0, 2^32))", seed, stream_id, round);
+  PAIG_REQUIRE(m >= 0 && m <= 0x7fffffffLL * 64, "synth_draw: m=%lld", m);
+  if (m == 0) return 0;
+  PAIG_REQUIRE(p0 && v0, "synth_draw: null operand");
+  const dim3 grid((unsigned)((m + 63) / 64)), block(64);
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)stream_id, rd = (uint32_t)round;
+  if (phys == PHYS_SPRING)
+    hipLaunchKernelGGL((synth_draw_k<2, PHYS_SPRING>), grid, block, 0, st, k0, k1, rd, m, half, size, radius, c0, c1,
+                       vmax, p0, v0, u);
+  else if (phys == PHYS_BOUNCE)
+    hipLaunchKernelGGL((synth_draw_k<2, PHYS_BOUNCE>), grid, block, 0, st, k0, k1, rd, m, half, size, radius, c0, c1,
+                       vmax, p0, v0, u);
+  else
+    hipLaunchKernelGGL((synth_draw_k<3, PHYS_GRAVITY>), grid, block, 0, st, k0, k1, rd, m, half, size, radius, c0, c1,
+                       vmax, p0, v0, u);
+  PAIG_CHECK_LAUNCH();
+  return 0;
+}
+
+int paig_synth_background(long long seed, long long stream_id, long long round, long long n, int size, float* bg,
+                          void* stream) {
+  PAIG_REQUIRE(seed >= 0 && seed <= 0xffffffffLL && stream_id >= 0 && stream_id <= 0xffffffffLL && round >= 0 &&
+                   round <= 0xffffffffLL,
+               "synth_background: seed=%lld stream=%lld round=%lld (each in [0, 2^32))", seed, stream_id, round);
+  PAIG_REQUIRE(n >= 0 && size > 0 && size % 4 == 0 && size <= 4096, "synth_background: n=%lld size=%d", n, size);
+  if (n == 0) return 0;
+  PAIG_REQUIRE(bg && ((uintptr_t)bg % 16) == 0, "synth_background: bg must be 16-byte aligned");
+  const long long quads = n * (long long)(size * size / 4);
+  PAIG_REQUIRE(quads <= 0x7fffffffLL * 256, "synth_background: n=%lld too large", n);
+  hipLaunchKernelGGL(synth_bg_k, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (uint32_t)seed, (uint32_t)stream_id, (uint32_t)round, quads, bg);
+  PAIG_CHECK_LAUNCH();
+  return 0;
+}
+
+int paig_synth_compact(const int* valid, long long m, long long* rows, long long n, int* count, long long* totals,
+                       void* stream) {
+  PAIG_REQUIRE(m >= 0 && m <= 0x7fffffffLL && n >= 0, "synth_compact: m=%lld n=%lld", m, n);
+  PAIG_REQUIRE(count && (m == 0 || valid) && (n == 0 || rows), "synth_compact: null operand");
+  hipLaunchKernelGGL(synth_compact_k, dim3(1), dim3(256), 0, (hipStream_t)stream, valid, m, rows, n, count, totals);
   PAIG_CHECK_LAUNCH();
   return 0;
 }

@@ -164,6 +164,220 @@ class DeviceDataIterator(DataIterator):
         return self._gather(np.arange(self.start_idx, min(self.start_idx + batch_size, self.num_examples))), None
 
 
+class StreamPlan:
+    """The schedule of ``StreamingDeviceIterator``, without a GPU: which
+    events to record and wait on and which half to refill with which batch at
+    every ``next_batch`` call, as data.
+
+    The pool has ``depth`` halves of ``B`` slots; batch k lives in half
+    k % depth.  ``start()`` is the construction (batches 0 .. depth - 1 filled
+    synchronously).  Call number k of ``next(batch_size)`` returns, in issue
+    order:
+
+      ("record", "done", k - 1)        compute stream: step k - 1 has ended   (k >= 1)
+      ("refill", half, batch, ("done", k - 1))
+                                       refill stream: wait for that event, then
+                                       write batch k - 1 + depth into half
+                                       (k - 1) % depth and record its "filled"
+                                       event -- under step k                  (k >= 1)
+      ("wait", "filled", half, k)      compute stream: batch k is in half k % depth
+      ("gather", half, k)              compute stream: the gather launch
+
+    so a half is rewritten only after the step that read it, and read only
+    after the refill that wrote it.  Epochs are nominal: ``epochs_completed``
+    advances every ``epoch_size // (B * world)`` batches."""
+
+    def __init__(self, depth, B, epoch_size, world=1):
+        self.depth, self.B, self.world = int(depth), int(B), int(world)
+        if self.depth < 1 or self.B < 1 or self.world < 1:
+            raise ValueError(f"StreamPlan: depth={depth} B={B} world={world}")
+        self.epoch_batches = int(epoch_size) // (self.B * self.world)
+        if self.epoch_batches < 1:
+            raise ValueError(f"StreamPlan: epoch_size={epoch_size} holds no batch of {self.B} x {self.world} ranks")
+        self.k = 0                  # next_batch calls so far
+        self.in_epoch = 0
+        self.epochs_completed = 0
+
+    def start(self):
+        return [("fill", j % self.depth, j) for j in range(self.depth)]
+
+    def next(self, batch_size):
+        if int(batch_size) != self.B:
+            raise ValueError(f"a streaming iterator serves batches of {self.B} only, not {batch_size}")
+        k, d = self.k, self.depth
+        ops = []
+        if k >= 1:
+            ops.append(("record", "done", k - 1))
+            ops.append(("refill", (k - 1) % d, k - 1 + d, ("done", k - 1)))
+        ops.append(("wait", "filled", k % d, k))
+        ops.append(("gather", k % d, k))
+        self.k += 1
+        self.in_epoch += 1
+        if self.in_epoch == self.epoch_batches:
+            self.in_epoch = 0
+            self.epochs_completed += 1
+        return ops
+
+    def reset_epoch(self):
+        self.in_epoch = 0
+        self.epochs_completed = 0
+
+
+class StreamingDeviceIterator(DeviceDataIterator):
+    """An unlimited, never-repeating training stream rendered on the device
+    (csrc/synth.hip), living in ``depth`` batches of HBM.
+
+    ``X`` is the pool, uint8 [depth * B, T, H, W, 3]; batch k is read from
+    slots (k % depth) * B .. through a persistent device index tensor, by the
+    gather of ``DeviceDataIterator`` (``bind_targets`` / ``ByteTargets`` work
+    unchanged: the decoders read the pool's rows).  While step k runs, the
+    half that step k - 1 read is refilled with batch k - 1 + depth on a stream
+    of the iterator's own (``StreamPlan``): draw (``paig_synth_draw``, Philox
+    key (seed, rank), round = the batch number) -> integrate -> compact ->
+    raster, all into buffers allocated here once.  A refill allocates nothing,
+    synchronises nothing and reads nothing back; the host's work per batch is
+    the launches.  The stream is a function of (task, seq_len, B, candidates,
+    seed, rank) alone.
+
+    Shortfall: a refill that accepts fewer than B of its ``candidates`` writes
+    the slots it has rows for; the others keep their previous, still valid
+    sequence.  The device counts such slots; ``stats()`` (which synchronises)
+    reads the counters.  ``candidates`` defaults to
+    ``synth_device.default_candidates`` (expected accepted >= 1.5 B).
+
+    Lifetime: batch k -- the gathered floats' source and, with byte targets
+    bound, the pool rows the decoders of the step read -- stays valid until
+    the ``next_batch`` call after the one that returned it: that call orders
+    the refill of batch k's half after everything queued before it on the
+    stream that is current then.  So a step must be queued on that stream
+    before the next ``next_batch`` call, and a caller that reads a half after
+    its next ``next_batch`` call is unsupported (it may see the next batch's
+    bytes).  Refills are never captured into a graph, and none runs during
+    ``GraphStep.capture()``: they are issued by ``next_batch`` only, and the
+    capture synchronises the device first.  ``num_examples`` is the nominal
+    epoch size; ``next_batch`` with any batch size other than B raises."""
+
+    TOPUP_ROUND0 = 1 << 31   # the Philox rounds of construction top-ups: batch numbers stay below
+
+    def __init__(self, task, seq_len, batch_size, device, epoch_size, seed=0, rank=0, world=1, depth=2,
+                 candidates=None, radius=2.0):
+        import torch
+        from . import synth_device as S
+        q = S.task_params(task, radius)
+        self.task, self.q, self.radius = task, q, radius
+        self.B, self.T, self.depth = int(batch_size), int(seq_len), int(depth)
+        size, K = q["size"], q["K"]
+        self.plan = StreamPlan(self.depth, self.B, epoch_size, world)
+        self.key = (int(0 if seed is None else seed), int(rank))
+        self.candidates = int(candidates) if candidates else S.default_candidates(task, self.T, self.B, radius=radius)
+        dev = torch.device(device)
+        X = torch.zeros((self.depth * self.B, self.T, size, size, 3), dtype=torch.uint8, device=dev)
+        super().__init__(X, (self.T, 3, size, size), dev, seed=seed, rank=rank, world=world)
+        self.num_examples = int(epoch_size)
+        m = self.candidates
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.p0, self.v0 = torch.empty((m, K, 2), **f64), torch.empty((m, K, 2), **f64)
+        self.pos = torch.empty((m, self.T, K, 2), **f64)
+        self.valid = torch.empty((m,), dtype=torch.int32, device=dev)
+        self.rows = torch.empty((self.B,), dtype=torch.int64, device=dev)
+        self.count = torch.zeros((2,), dtype=torch.int32, device=dev)
+        self.totals = torch.zeros((3,), dtype=torch.int64, device=dev)
+        self.bg = torch.empty((self.B, size, size), dtype=torch.float32, device=dev) \
+            if task == "mnist_spring_color" else None
+        self.refill_stream = torch.cuda.Stream(device=dev)
+        self.filled = [torch.cuda.Event() for _ in range(self.depth)]
+        self.done = torch.cuda.Event()
+        self.construction_rounds = 0
+        self._construct()
+
+    def reset_iteration(self):
+        # no permutation: the pool's slots in order, uploaded once
+        import torch
+        if self.idx_d is None:
+            self.idx_d = torch.arange(self.X.shape[0], dtype=torch.int64, device=self.device)
+        self.start_idx = 0
+
+    def reset_epoch(self):
+        self.plan.reset_epoch()
+        self.epochs_completed = 0
+
+    def _render(self, round, out, rows, totals):
+        """One round on the current stream: candidates of Philox round
+        ``round`` -> the accepted ones' frames into ``out`` [n, ...]."""
+        from . import synth_device as S
+        seed, rank = self.key
+        S.draw_device(self.task, seed, rank, round, self.candidates, radius=self.radius, p0=self.p0, v0=self.v0)
+        S.integrate_device(self.task, self.p0, self.v0, self.T, self.radius, pos=self.pos, valid=self.valid)
+        S.compact_device(self.valid, rows.shape[0], rows=rows, count=self.count, totals=totals)
+        bg = None
+        if self.bg is not None:
+            bg = S.background_device(seed, rank, round, self.bg)[:rows.shape[0]]
+        S.rasterize_rows_device(self.pos, self.q["size"], self.q["draw"], rows, out, bg=bg)
+
+    def _construct(self):
+        """Fill every slot, synchronously: half h from round h; a half whose
+        round accepted fewer than B is topped up from the rounds
+        TOPUP_ROUND0, TOPUP_ROUND0 + 1, .. until each slot is written once."""
+        import torch
+        B, topup = self.B, self.TOPUP_ROUND0
+        # the pool and the counters were zeroed on the current stream
+        self.refill_stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.device(self.device), torch.cuda.stream(self.refill_stream):
+            for _, h, j in self.plan.start():
+                have, round = 0, j
+                while have < B:
+                    self._render(round, self.X[h * B + have:(h + 1) * B], self.rows[:B - have], None)
+                    self.construction_rounds += 1
+                    have += int(self.count[0].item())   # construction only: a sync per round
+                    round, topup = topup, topup + 1
+                self.filled[h].record(self.refill_stream)
+        self.refill_stream.synchronize()
+
+    def _refill(self, half, batch):
+        import torch
+        with torch.cuda.stream(self.refill_stream):
+            self._render(batch, self.X[half * self.B:(half + 1) * self.B], self.rows, self.totals)
+            self.filled[half].record(self.refill_stream)
+
+    def next_batch(self, batch_size, data_type="train", shuffle=True, out=None):
+        import torch
+        from paig_reproduction_amd._lib import PaigError
+        assert data_type in ["train", "val", "test"], "data_type must be 'train', 'val', or 'test'."
+        try:
+            ops = self.plan.next(batch_size)
+        except ValueError as e:
+            raise PaigError(str(e)) from None
+        B = self.B
+        out = self._out(B, out)
+        with torch.cuda.device(self.device):
+            compute = torch.cuda.current_stream(self.device)
+            for op in ops:
+                if op[0] == "record":
+                    self.done.record(compute)
+                elif op[0] == "refill":
+                    self.refill_stream.wait_event(self.done)
+                    self._refill(op[1], op[2])
+                elif op[0] == "wait":
+                    compute.wait_event(self.filled[op[2]])
+                else:
+                    self._launch(self.idx_d.data_ptr() + 8 * op[1] * B, B, out)
+        self.epochs_completed = self.plan.epochs_completed
+        return out, None
+
+    def sample_random_batch(self, batch_size):
+        from paig_reproduction_amd._lib import PaigError
+        raise PaigError("a streaming iterator has no resident dataset to sample from")
+
+    def stats(self):
+        """Synchronises the refill stream and reads the device counters:
+        refills since construction, the accepted sequences they wrote (mean per
+        refill) and the slots they left with their previous sequence."""
+        self.refill_stream.synchronize()
+        r, acc, short = (int(v) for v in self.totals.cpu().tolist())
+        return {"refills": r, "accepted_per_refill": acc / r if r else float("nan"), "shortfall_slots": short,
+                "candidates": self.candidates, "construction_rounds": self.construction_rounds}
+
+
 class ByteTargets:
     """The decoders' targets read from the device-resident dataset (SURVEY §8
     F2 + the fused SSE): a batch gathered into the bound buffer ``xbuf``

@@ -208,6 +208,9 @@ class BaseNetTorch(torch.nn.Module):
                 print("eval running")
                 valid_metrics_results = self.eval_performance(batch_size, type='valid')
                 log_metrics(logger, "valid - epoch=%s" % ep, valid_metrics_results)
+                if hasattr(self.train_iterator, "stats"):   # a streaming iterator: one sync, here only
+                    logger.info("stream - epoch=%s " % ep +
+                                " ".join(f"{k}={v:.4g}" for k, v in self.train_iterator.stats().items()))
 
             if ep % save_every_n_epochs == 0:
                 print("saving")

@@ -30,6 +30,13 @@ Additive flags only:
         integrators + rasteriser) and keep it in HBM; no npz is written.  Same
         distribution as synth.py, other sequences.  Under data parallelism every
         rank renders the same dataset and takes its shard.  0 (default): as before.
+  --synthetic_stream {0,1}       1: with --synthetic N and --device_data 1, the training split
+        is an unlimited stream rendered on the GPU while the previous step runs
+        (StreamingDeviceIterator: two batches of HBM, no batch seen twice, N the nominal
+        epoch size; under data parallelism every rank streams its own data).  Valid and test
+        are rendered once on the device (N//10 each) and stay resident.  Nothing is read
+        from or written to --data_dir; the stream's statistics are logged at every
+        evaluation.  0 (default): as before.
 
 Data-parallel training: launch with torchrun (one process per GPU, RCCL);
 --batch_size is per rank, every rank draws a disjoint shard of each epoch.
@@ -113,6 +120,9 @@ def build_parser():
                    help="1: dataset resident in HBM as uint8, batches gathered on the GPU (F2); 0: host iterators")
     p.add_argument("--synthetic_device", type=int, choices=(0, 1), default=0,
                    help="1: render a missing --synthetic dataset on the GPU and keep it there (no npz written)")
+    p.add_argument("--synthetic_stream", type=int, choices=(0, 1), default=0,
+                   help="1: stream never-repeating training batches from the device renderer (needs --synthetic N, "
+                        "the nominal epoch size, and --device_data 1); nothing touches --data_dir")
     p.add_argument("--sigma", type=float, default=1.0,
                    help="decoder attention-window scale (PhysicsNet.log_sig), in [0.5, 2]: 2 halves the window")
     p.add_argument("--learn_sigma", action="store_true",
@@ -163,8 +173,14 @@ def _rank():
     return dist.get_rank() if dist.is_initialized() else 0
 
 
-def iterators(args, rel, seq_len, rank, world, device):
-    """The task's train / valid / test iterators for sequences of seq_len."""
+def iterators(args, rel, seq_len, rank, world, device, train=True):
+    """The task's train / valid / test iterators for sequences of seq_len
+    (train=False: the test pass, which reads the test split only)."""
+    if args.synthetic_stream:
+        from paig_reproduction_amd.nn.datasets.synth_device import streaming_iterators
+        n = args.synthetic
+        return streaming_iterators(args.task, seq_len, args.batch_size, n, max(n // 10, 1), max(n // 10, 1), args.seed,
+                                   device, rank=rank, world=world, data_seed=0, stream=train)
     if args.synthetic_device and args.synthetic > 0 and not os.path.exists(os.path.join(args.data_dir, rel)):
         from paig_reproduction_amd.nn.datasets.synth_device import device_iterators
         n = args.synthetic
@@ -176,6 +192,8 @@ def iterators(args, rel, seq_len, rank, world, device):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.synthetic_stream and not (args.synthetic > 0 and args.device_data):
+        raise SystemExit("--synthetic_stream 1 needs --synthetic N (the epoch size) and --device_data 1")
     logger = logging.getLogger("torch")
     logger.setLevel(logging.DEBUG)
     if not logger.handlers:
@@ -229,7 +247,7 @@ def main(argv=None):
     network = make(test_seq_len)
     network.build_optimizer(args.base_lr, args.optimizer, args.anneal_lr, **optim)
     network.initialize_graph(args.save_dir, True, args.ckpt_dir)
-    its = iterators(args, test_data_file, test_seq_len, rank, world, device)
+    its = iterators(args, test_data_file, test_seq_len, rank, world, device, train=False)
     network.get_data(its)
     network.train_model(0, args.batch_size, args.save_every_n_epochs, args.eval_every_n_epochs,
                         args.print_interval, args.debug)
