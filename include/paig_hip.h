@@ -162,8 +162,22 @@ int paig_conv2d_wgrad_ex(const float* x, long long x_fs, int x_grp, long long x_
  *   backward before use -- dy * ReLU'(y) + scatter of dpool [F][Cout][H/2][W/2]
  *   to the argmax -- from the window codes pcode (paig_conv2d_fwd_pwc) of the
  *   forward's fused pool (replaces paig_maxpool2_bwd_relu).
+ * flags & 1024 (opt-in row layout): each slab row in the kernel's accumulator
+ *   order instead -- the 16 x 16 weight-gradient fragment (m, nt) as 256
+ *   floats at ((m*NTX + nt)*64 + lane)*4 + r (MT = ceil(Cout/16), NTX =
+ *   ceil(9*Cin/16) fragments; element = dW[16m + 4(lane/16) + r][ci][tap] of
+ *   column 16nt + lane%16 = 4(tap*Cin/4 + ci/4) + ci%4; padding rows / columns
+ *   hold unspecified values), then the Cout bias partials.  One 16-byte store
+ *   per lane (1 KB per wave instruction) instead of 4-byte scatters.  Rows of
+ *   paig_conv2d_bwd_slab_len(Cin, Cout, ks, flags) floats, slab 16-byte
+ *   aligned; paig_slab_reduce_multi_frag sums them into [Cout*Cin*9 | Cout],
+ *   the same bits as the default rows through paig_slab_reduce_multi.
+ *   paig_conv2d_bwd_supported(.., flags | 1024) says which shapes take it
+ *   (all but the plain 8 -> 8 at 36 x 36 in split arithmetic).
  * Shapes: paig_conv2d_bwd_supported. */
 int paig_conv2d_bwd_supported(int Cin, int Cout, int H, int W, int ks, int flags);
+/* floats per slab row of paig_conv2d_bwd with these flags (0: no such layer) */
+size_t paig_conv2d_bwd_slab_len(int Cin, int Cout, int ks, int flags);
 int paig_conv2d_bwd(const float* x, long long x_fs, int x_grp, long long x_gs, const float* dy, long long dy_fs,
                     float* dx, long long dx_fs, const float* aux, long long aux_fs, const float* w, float* slab,
                     int nblk_max, int* nblk_out, int F, int Cin, int Cout, int H, int W, int ks, int flags,
@@ -373,6 +387,15 @@ int paig_slab_reduce(const float* slab, int nblk, long long ld, int len, float* 
 /* up to 32 independent deterministic slab reductions in one launch (host arrays of ntask entries) */
 int paig_slab_reduce_multi(int ntask, const float* const* src, const int* nblk, const int* len, float* const* dst,
                            int accumulate, void* stream);
+/* paig_slab_reduce_multi whose tasks with cin[t] > 0 hold rows in the fused
+ * layer backward's accumulator order (paig_conv2d_bwd flags & 1024; len[t] =
+ * paig_conv2d_bwd_slab_len(cin[t], cout[t], 3, 1024), src[t] 16-byte aligned)
+ * and write dst[t] as [Cout*Cin*9 | Cout]: rows are read and summed exactly as
+ * the plain rows are (same path, row order and tree), each sum is written to
+ * its own place and the padding dropped.  cin[t] = 0 (or null arrays): a
+ * plain task. */
+int paig_slab_reduce_multi_frag(int ntask, const float* const* src, const int* nblk, const int* len,
+                                float* const* dst, const int* cin, const int* cout, int accumulate, void* stream);
 int paig_axpby(const float* x, float* y, long long n, float a, float b, void* stream);
 
 /* VariableFromNetwork: y = W2 tanh(W1 ones + b1) + b2 (ypost = sigmoid(y) if given) */

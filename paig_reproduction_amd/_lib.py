@@ -44,6 +44,7 @@ SIGNATURES = {
     "paig_conv2d_mfma_supported": (I, [I, I, I, I, I, I, I]),
     "paig_debug_fwd_block_cap": (I, [I]),
     "paig_conv2d_bwd_supported": (I, [I, I, I, I, I, I]),
+    "paig_conv2d_bwd_slab_len": (SZ, [I, I, I, I]),
     "paig_conv2d_bwd": (I, [P, LL, I, LL, P, LL, P, LL, P, LL, P, P, I, P, I, I, I, I, I, I, I, P, I, P, LL, P, LL,
                             P, P]),
     "paig_conv2d_fwd_pwc": (I, [P, LL, I, LL, P, LL, P, LL, P, P, I, I, I, I, I, I, I, P, I, P, LL, P, LL, P, P]),
@@ -103,6 +104,7 @@ SIGNATURES = {
     "paig_colsum": (I, [P, I, I, LL, P, I, P, P]),
     "paig_slab_reduce": (I, [P, I, LL, I, P, I, P]),
     "paig_slab_reduce_multi": (I, [I, P, P, P, P, I, P]),
+    "paig_slab_reduce_multi_frag": (I, [I, P, P, P, P, P, P, I, P]),
     "paig_axpby": (I, [P, P, LL, F32, F32, P]),
     "paig_vfn_fwd": (I, [P, P, P, P, P, P, P, I, P]),
     "paig_vfn_bwd_blocks": (I, [I]),
@@ -185,7 +187,7 @@ GN_NORM, GN_COEF, GN_NONFINITE, GN_TOTAL_SQ, GN_GROUP0, GN_SQ0 = 0, 1, 2, 3, 4, 
 
 _QUERY = {"paig_last_error", "paig_abi_version", "paig_f16_range_status", "paig_conv2d_mfma_supported",
           "paig_debug_fwd_block_cap",
-          "paig_conv2d_bwd_supported", "paig_velmlp_bwd_blocks",
+          "paig_conv2d_bwd_supported", "paig_conv2d_bwd_slab_len", "paig_velmlp_bwd_blocks",
           "paig_velmlp_slab_len", "paig_head_bwd_blocks", "paig_head_l2_bwd_blocks", "paig_head_mask_blocks", "paig_conv_wprep_size", "paig_gemm_workspace", "paig_colsum_workspace",
           "paig_gemm_parts_size", "paig_gemm_parts", "paig_unet_workspace", "paig_unet_workspace_ex",
           "paig_unet_buffer", "paig_unet_query", "paig_localiser_workspace",

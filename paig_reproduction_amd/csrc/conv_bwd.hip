@@ -58,10 +58,13 @@
 // s_memtime cycle sums of the tile loop's phases (0 setup, 1 prefetch wait +
 // max + barrier, 2 commit, 3 issue, 4 weight gradient, 5 data gradient, 6
 // epilogue, 7 slab write; inside the commit: 8 dY staging, 9 UPS window +
-// halo, 10 its barrier, 11 the upsampled X staging) and the tile count, stored
-// by lane 0 (vector stores)
+// halo, 10 its barrier, 11 the upsampled X staging), the tile count (12) and
+// the once-per-block phases split further (setup: 13 halo zeroing, 14 weight
+// image copy, 15 addressing, 16 first issue, 17 xmax reduction, 0 the rest;
+// slab: 18 the whole N-tiles' stores, 19 the tail N-tile reduction + stores, 7
+// the bias reduction), stored by lane 0 (vector stores)
 #ifdef PAIG_BWD_STAMPS
-__device__ unsigned long long paig_bwd_stamps[4096][4][13];
+__device__ unsigned long long paig_bwd_stamps[4096][4][20];
 #define PAIG_BSTAMP(k)                                      \
   do {                                                      \
     const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
@@ -141,6 +144,20 @@ constexpr bool sbwd_hoist(int CIN, int COUT, int H, int PM, bool PF) {
   return true;
 }
 
+// floats of a slab row in accumulator order (flags & 1024): the 16 x 16
+// weight-gradient fragments (MT x NTX, 256 floats each), then the bias
+constexpr int sbwd_frag_len(int CIN, int COUT) {
+  return ceil_div(COUT, 16) * ceil_div(9 * (rup(CIN, 4) / 4), 4) * 256 + COUT;
+}
+// the shapes that compile that row layout's stores next to the default ones.
+// Not 3bp's plain 8 -> 8 at 36 x 36: it has no register to spare at three
+// blocks per CU (measured: -Rpass-analysis=kernel-resource-usage shows 8
+// bytes of scratch with the second store path, none without), and its rows
+// would double anyway (Cout = 8: half of each fragment is padding)
+constexpr bool sbwd_fragrows(int CIN, int COUT, int H, int PM, bool PF) {
+  return !(CIN == 8 && COUT == 8 && H == 36 && PM == 0 && !PF);
+}
+
 // 4 waves split the weight-gradient N-tiles (each wave owns every 4th one
 // over all pixels: no cross-wave reduction); the data gradient's M-tiles of
 // 16 pixels are split over the waves as in the dgrad kernel
@@ -191,6 +208,8 @@ struct SBwdCfg {
   static constexpr int NTF = BAL ? NTX / 4 : ceil_div(NTX, 4), NTR = BAL ? NTX % 4 : 0;
   static constexpr int KB = ceil_div(TPXV, 32);
   static constexpr int NCOL = CIN * KK, SLAB = COUT * NCOL + COUT;
+  static constexpr int SLABF = sbwd_frag_len(CIN, COUT);   // the row in accumulator order (flags & 1024)
+  static constexpr bool FRAG = sbwd_fragrows(CIN, COUT, H, PM, PF);
   // ---- staging units: UPX pixels x (8 dY | 4 X) channels, pixel fastest
   static constexpr int UPX = W % 2 == 0 ? 2 : 1, W2 = W / UPX;
   static constexpr int NID = FPT * ROWSD * W2 * CCD, NLD = ceil_div(NID, 256);
@@ -262,7 +281,7 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4;
   __shared__ float smax[4];
 #ifdef PAIG_BWD_STAMPS
-  unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = __builtin_amdgcn_s_memtime(), st_n = 0;
+  unsigned long long st_acc[20] = {}, st_last = __builtin_amdgcn_s_memtime(), st_n = 0;
 #endif
 
   auto xplane = [](int cq) { return cq * XPL + ((cq & 1) ? 16 : 0) + ((cq & 2) ? 64 : 0); };
@@ -290,6 +309,7 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
     }
   };
   zero_xhalo();
+  PAIG_BSTAMP(13);
 
   // ---- scales (PM 0): X per launch (ecx), dY per tile (ecd), the
   // data-gradient weights per output channel (ewn)
@@ -362,6 +382,7 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
     }
   }
 
+  PAIG_BSTAMP(14);
   // ---- data-gradient fragment offsets (slots): pixel base per M-tile,
   // (tap, chunk) per k-step
   int pbase[MW];
@@ -854,7 +875,9 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
 
   int lt = blockIdx.x;
   auto tile_of =[&](int l) { return l < ntiles ? xcd_tile(l, ntiles) : ntiles; };
+  PAIG_BSTAMP(15);
   issue(tile_of(lt));
+  PAIG_BSTAMP(16);
   if (PM == 0 && xm.p) {
     // the launch's X exponent: max over the forward's per-block slots
     float m = 0.f;
@@ -869,6 +892,7 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
     if (m > 0.f) ecx = f16_scale_exp(m);   // all-zero slots (never written): the fixed scale, guarded
     __syncthreads();
   }
+  PAIG_BSTAMP(17);
   if constexpr (PM == 0) xsc = __builtin_amdgcn_ldexpf(1.f, ecx);
   else ecx = 0;
 
@@ -1143,8 +1167,23 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
 
   // ---- this block's slab row: weight gradients (each wave its N-tiles,
   // scaled back exactly), then the bias
-  float* s = slab + (long long)blockIdx.x * C::SLAB;
+  // flags & 1024: the row in accumulator order -- fragment (m, nt) as one
+  // f32x4 per lane at float ((m NTX + nt) 64 + lane) 4 (1 KB contiguous per
+  // wave store instead of 64 scattered floats), padding rows / columns as
+  // computed, the bias after the MT NTX fragments; the reduction permutes
+  // (paig_slab_reduce_multi_frag)
+  const bool frag = C::FRAG && (flags & 1024) != 0;
+  float* s = slab + (long long)blockIdx.x * (frag ? C::SLABF : C::SLAB);
   auto put_w = [&](int m, int nt, const f32x4& acc) __attribute__((always_inline)) {
+    if (frag) {
+      f32x4 v = acc;
+      if constexpr (PM == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = __builtin_amdgcn_ldexpf(v[r], -(ecx + ecd));
+      }
+      *reinterpret_cast<f32x4*>(s + ((m * NTX + nt) * 64 + lane) * 4) = v;
+      return;
+    }
     const int col = nt * 16 + (lane & 15), cq = col >> 2;
     const int tap = cq / CQ, ci = (cq % CQ) * 4 + (col & 3);
 #pragma unroll
@@ -1160,6 +1199,7 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
 #pragma unroll
     for (int j = 0; j < NTF; ++j)
       if (wv + j * 4 < NTX) put_w(m, wv + j * 4, accw[m][j]);
+  PAIG_BSTAMP(18);
   if constexpr (NTR > 0) {
     // tail N-tiles: the 4 waves' k-block partials, summed in wave order
     f32x4* Rt = reinterpret_cast<f32x4*>(lds16);   // [4][MT][NTR][64]
@@ -1176,6 +1216,7 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
       put_w(u / NTR, NTF * 4 + u % NTR, v);
     }
   }
+  PAIG_BSTAMP(19);
   // bias: unit i of thread i % 256 (slot i / 256) kept the partials of its 8
   // channels.  Two fixed-order stages: thread (channel co, part q) sums the
   // units q, q + NP, ... of co's chunk; thread co then sums its NP parts
@@ -1201,14 +1242,14 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
   if (tid < COUT) {
     float v = 0.f;
     for (int q = 0; q < NP; ++q) v += Rp[tid * NP + q];
-    s[COUT * NCOL + tid] = v;
+    s[(frag ? C::SLABF - COUT : COUT * NCOL) + tid] = v;
   }
   if constexpr (PM == 0) f16_range_note(rmax);
 #ifdef PAIG_BWD_STAMPS
   PAIG_BSTAMP(7);
   if (lane == 0 && blockIdx.x < 4096) {
 #pragma unroll
-    for (int k = 0; k < 12; ++k) paig_bwd_stamps[blockIdx.x][wv][k] = st_acc[k];
+    for (int k = 0; k < 20; ++k) paig_bwd_stamps[blockIdx.x][wv][k] = st_acc[k];
     paig_bwd_stamps[blockIdx.x][wv][12] = st_n;
   }
 #endif
@@ -1254,6 +1295,7 @@ static int sbwd_launch(FView x, FView dy, FViewW dx, FView aux, const float* w, 
   PAIG_REQUIRE(!xm.p || (xm.n % 4 == 0 && (reinterpret_cast<uintptr_t>(xm.p) & 15) == 0),
                "conv split bwd: xmax needs 16-byte alignment and a multiple of 4 slots (%d)", xm.n);
   PAIG_REQUIRE(!(flags & 2) || aux.p, "conv split bwd: ReLU' mask (flags & 2) without aux");
+  PAIG_REQUIRE(C::FRAG || !(flags & 1024), "conv split bwd: no rows in accumulator order (flags & 1024) for this shape");
   // the prefetch addresses a tile's frames by 32-bit byte offsets from the
   // tile's first frame (descriptors rebased per tile: no bound on F)
   constexpr long long SPAN = (1ll << 31) / (4 * C::FPT) - 8 * 4096;
@@ -1294,6 +1336,7 @@ extern "C" {
 
 int paig_conv2d_bwd_supported(int Cin, int Cout, int H, int W, int ks, int flags) {
   if (H != W || ks != 3 || !(flags & (128 | 256))) return 0;
+  if ((flags & 1024) && !sbwd_fragrows(Cin, Cout, H, flags & 256 ? 2 : 0, (flags & 64) != 0)) return 0;
 #define PAIG_CASE(CI, CO, HH) \
   if (Cin == CI && Cout == CO && H == HH) return 1;
   if (flags & 64) {
@@ -1308,6 +1351,11 @@ int paig_conv2d_bwd_supported(int Cin, int Cout, int H, int W, int ks, int flags
   PAIG_BWD_SHAPES(PAIG_CASE)
 #undef PAIG_CASE
   return 0;
+}
+
+size_t paig_conv2d_bwd_slab_len(int Cin, int Cout, int ks, int flags) {
+  if (ks != 3 || Cin <= 0 || Cout <= 0) return 0;
+  return flags & 1024 ? (size_t)sbwd_frag_len(Cin, Cout) : (size_t)Cout * Cin * 9 + Cout;
 }
 
 int paig_conv2d_bwd(const float* x, long long x_fs, int x_grp, long long x_gs, const float* dy, long long dy_fs,
@@ -1327,7 +1375,9 @@ int paig_conv2d_bwd(const float* x, long long x_fs, int x_grp, long long x_gs, c
   FViewW vdx{dx, dx_fs};
   XMax xm{const_cast<float*>(xmax), xmax_n};
   const bool b16 = (flags & 256) != 0;
-  const int fl = flags & 6;
+  const int fl = flags & (6 | 1024);
+  PAIG_REQUIRE(!(flags & 1024) || (reinterpret_cast<uintptr_t>(slab) & 15) == 0,
+               "paig_conv2d_bwd: rows in accumulator order (flags & 1024) need a 16-byte aligned slab");
   if (flags & 64) {
     const FView vp{dpool, dpool_fs, 0, 0};
 #define PAIG_CASE(CI, CO, HH)                                                                                     \

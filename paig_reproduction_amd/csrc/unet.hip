@@ -18,6 +18,7 @@
 // nothing.
 #include "common.h"
 
+#include <algorithm>
 #include <vector>
 
 #define UNET_HIP(call)                                                  \
@@ -208,6 +209,15 @@ bool pool_folded(const UPlan& p, int i, int H, int cm, int flags) {
 
 constexpr int NBLK_MAX = 1024;   // slab rows per conv (engine.py: nblk_max)
 size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
+// The fused layer backward's slab rows in accumulator order (paig_conv2d_bwd
+// flags & 1024: 16-byte stores, permuted by the batched reduction) where the
+// padding of the 16 x 16 fragments adds at most 1/8 to the row: every layer
+// with Cout >= 16.  The rows of the Cout = 8 layers (c2, c11, c12) would
+// double, and with them the bytes the launch writes and the reduction reads
+int bwd_row_flag(int cin, int cout, int ks) {
+  const size_t plain = paig_conv2d_bwd_slab_len(cin, cout, ks, 0), fr = paig_conv2d_bwd_slab_len(cin, cout, ks, 1024);
+  return plain > 0 && fr <= plain + plain / 8 ? 1024 : 0;
+}
 
 // Workspace layout (bytes), shared by the query and both calls
 struct ULayout {
@@ -246,7 +256,11 @@ void layout(const UPlan& p, ULayout& L, int F, int H, int cm, int flags) {
     const UOp& op = p.ops[i];
     if (op.kind != U_CONV) continue;
     const int cin = op.src.n, cout = op.dst.n, ks = op.ks;
-    if (train) L.slab[i] = take((size_t)NBLK_MAX * (cout * cin * ks * ks + cout) * 4);
+    if (train) {
+      size_t row = (size_t)cout * cin * ks * ks + cout;
+      if (bwd_row_flag(cin, cout, ks)) row = std::max(row, paig_conv2d_bwd_slab_len(cin, cout, ks, 1024));
+      L.slab[i] = take((size_t)NBLK_MAX * row * 4);
+    }
     if (cm == 128 && !(flags & PAIG_UNET_EXT_WPREP)) {
       L.wprep0[i] = take((size_t)paig_conv_wprep_size(cin, cout, ks) * 2);
       if (op.src.buf != p.X0) L.wprep1[i] = take((size_t)paig_conv_wprep_size(cout, cin, ks) * 2);
@@ -470,7 +484,7 @@ int bwd_impl(int net, int F, int H, int K, int math, int flags, const float* x, 
   };
   auto mark = [&](const Reg& r) { written[r.buf].push_back({r.off, r.n}); };
   std::vector<const float*> s_src;
-  std::vector<int> s_nb, s_len;
+  std::vector<int> s_nb, s_len, s_cin, s_cout;   // (s_cin > 0: rows in accumulator order)
   std::vector<float*> s_dst;
   std::vector<bool> folded_up(no, false);
   for (int i = first; i >= 0; --i) {
@@ -503,6 +517,7 @@ int bwd_impl(int net, int F, int H, int K, int math, int flags, const float* x, 
         const Reg usrc = p.ops[ui].src;
         const View dxv = dview(usrc);
         PAIG_REQUIRE(state(usrc) == 0, "paig_unet_bwd: upsample source gradient already written (op %d)", i);
+        const int rfl = bwd_row_flag(cin, cout, ks);
         int flags2 = cm | 32, alvl;
         const float* aux = nullptr;
         long long aux_fs = 0;
@@ -515,11 +530,13 @@ int bwd_impl(int net, int F, int H, int K, int math, int flags, const float* x, 
           }
         pr(0, i, op.conv, PAIG_PROBE_CONV_BWD, cin, cout, Hl, flags2);
         rc = paig_conv2d_bwd(sv.p, sv.fs, sv.grp, sv.gs, dyv.p, dyv.fs, const_cast<float*>(dxv.p), dxv.fs, aux, aux_fs,
-                             w[op.conv], slab, NBLK_MAX, &nb, F, cin, cout, Hl, Hl, ks, flags2, xm, PAIG_XMAX_SLOTS,
+                             w[op.conv], slab, NBLK_MAX, &nb, F, cin, cout, Hl, Hl, ks, flags2 | rfl, xm, PAIG_XMAX_SLOTS,
                              nullptr, 0, nullptr, 0, wp1, stream);
         pr(1, i, op.conv, PAIG_PROBE_CONV_BWD, cin, cout, Hl, flags2);
         if (rc) return rc;
-        s_src.push_back(slab), s_nb.push_back(nb), s_len.push_back(n_w + cout), s_dst.push_back(dwb[op.conv]);
+        s_src.push_back(slab), s_nb.push_back(nb), s_dst.push_back(dwb[op.conv]);
+        s_len.push_back((int)paig_conv2d_bwd_slab_len(cin, cout, ks, rfl));
+        s_cin.push_back(rfl ? cin : 0), s_cout.push_back(rfl ? cout : 0);
         mark(usrc);
         folded_up[ui] = true;
         continue;
@@ -527,7 +544,7 @@ int bwd_impl(int net, int F, int H, int K, int math, int flags, const float* x, 
       if (op.src.buf != p.X0 && !xfl && cm && !sep && paig_conv2d_bwd_supported(cin, cout, Hl, Hl, ks, cm)) {
         // data and weight gradients in one launch
         const View dxv = dview(op.src);
-        const int mode = state(op.src);
+        const int mode = state(op.src), rfl = bwd_row_flag(cin, cout, ks);
         PAIG_REQUIRE(mode >= 0, "paig_unet_bwd: partially written gradient region (op %d)", i);
         int flags2 = cm | (mode == 1 ? 4 : 0), alvl;
         const float* aux = nullptr;
@@ -556,11 +573,13 @@ int bwd_impl(int net, int F, int H, int K, int math, int flags, const float* x, 
         }
         pr(0, i, op.conv, PAIG_PROBE_CONV_BWD, cin, cout, Hl, flags2);
         rc = paig_conv2d_bwd(sv.p, sv.fs, sv.grp, sv.gs, dyv.p, dyv.fs, const_cast<float*>(dxv.p), dxv.fs, aux, aux_fs,
-                             w[op.conv], slab, NBLK_MAX, &nb, F, cin, cout, Hl, Hl, ks, cm | (flags2 & 70), xm,
+                             w[op.conv], slab, NBLK_MAX, &nb, F, cin, cout, Hl, Hl, ks, cm | (flags2 & 70) | rfl, xm,
                              PAIG_XMAX_SLOTS, dpool, dpool_fs, pcode, pcode_fs, wp1, stream);
         pr(1, i, op.conv, PAIG_PROBE_CONV_BWD, cin, cout, Hl, flags2);
         if (rc) return rc;
-        s_src.push_back(slab), s_nb.push_back(nb), s_len.push_back(n_w + cout), s_dst.push_back(dwb[op.conv]);
+        s_src.push_back(slab), s_nb.push_back(nb), s_dst.push_back(dwb[op.conv]);
+        s_len.push_back((int)paig_conv2d_bwd_slab_len(cin, cout, ks, rfl));
+        s_cin.push_back(rfl ? cin : 0), s_cout.push_back(rfl ? cout : 0);
         mark(op.src);
         continue;
       }
@@ -587,6 +606,7 @@ int bwd_impl(int net, int F, int H, int K, int math, int flags, const float* x, 
       pr(1, i, op.conv, PAIG_PROBE_CONV_WGRAD, cin, cout, Hl, xfl | cm | (pf ? 64 : 0));
       if (rc) return rc;
       s_src.push_back(slab), s_nb.push_back(nb), s_len.push_back(n_w + cout), s_dst.push_back(dwb[op.conv]);
+      s_cin.push_back(0), s_cout.push_back(0);
       PAIG_REQUIRE(!pf || op.src.buf != p.X0, "paig_unet_bwd: pool fold on the input layer (op %d)", i);
       if (op.src.buf == p.X0) continue;   // no input gradient (Q10)
       const int ui = p.fused_up[i];
@@ -663,8 +683,10 @@ int bwd_impl(int net, int F, int H, int K, int math, int flags, const float* x, 
   // every conv's weight + bias gradient and the caller's extra partial-
   // gradient slabs: one batched deterministic reduction
   for (int e = 0; e < n_extra; ++e)
-    s_src.push_back(e_src[e]), s_nb.push_back(e_nb[e]), s_len.push_back(e_len[e]), s_dst.push_back(e_dst[e]);
-  return paig_slab_reduce_multi((int)s_src.size(), s_src.data(), s_nb.data(), s_len.data(), s_dst.data(), 0, stream);
+    s_src.push_back(e_src[e]), s_nb.push_back(e_nb[e]), s_len.push_back(e_len[e]), s_dst.push_back(e_dst[e]),
+        s_cin.push_back(0), s_cout.push_back(0);
+  return paig_slab_reduce_multi_frag((int)s_src.size(), s_src.data(), s_nb.data(), s_len.data(), s_dst.data(),
+                                     s_cin.data(), s_cout.data(), 0, stream);
 }
 
 }  // namespace

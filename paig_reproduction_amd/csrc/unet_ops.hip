@@ -855,16 +855,32 @@ struct SlabTasks {
   int nblk[PAIG_MAX_SLAB_TASKS];
   int len[PAIG_MAX_SLAB_TASKS];
   int vec[PAIG_MAX_SLAB_TASKS];  // 1: len % 4 == 0 and src/dst 16-B aligned -> float4 path
+  int cin[PAIG_MAX_SLAB_TASKS];  // > 0: rows in the fused layer backward's accumulator order (slab_frag_dst)
+  int cout[PAIG_MAX_SLAB_TASKS];
   int start[PAIG_MAX_SLAB_TASKS + 1];
   int ntask;
   int accumulate;
 };
 
+// Rows in accumulator order (paig_conv2d_bwd flags & 1024, conv_bwd.hip
+// put_w): element e = ((m NTX + nt) 64 + lane) 4 + r of the 16 x 16 fragment
+// (m, nt) is dW[co = 16 m + 4 (lane / 16) + r][ci][tap] of column 16 nt +
+// lane % 16 = 4 (tap CQ + ci / 4) + ci % 4; the bias follows the fragments.
+// Its place in the [Cout*Cin*9 | Cout] gradient, -1 for a padding row / column
+__device__ __forceinline__ int slab_frag_dst(int e, int cin, int cout) {
+  const int CQ = cin / 4, NQ = 9 * CQ, NTX = (NQ + 3) / 4, nfr = (cout + 15) / 16 * NTX * 256;
+  if (e >= nfr) return cout * cin * 9 + (e - nfr);
+  const int r = e & 3, ln = (e >> 2) & 63, f = e >> 8, nt = f % NTX, m = f / NTX;
+  const int col = nt * 16 + (ln & 15), cq = col >> 2, co = m * 16 + (ln >> 4) * 4 + r;
+  if (co >= cout || cq >= NQ) return -1;
+  return (co * cin + (cq % CQ) * 4 + (col & 3)) * 9 + cq / CQ;
+}
+
 // Scalar path (64 columns per block): 16 waves, each lane owns one column,
 // the waves stride the rows (4 independent accumulators each), then a
 // fixed-order combine.
 __device__ __forceinline__ void slab_cols_scalar(const float* __restrict__ src, float* dst, int len, int nblk,
-                                                 int blk, int accumulate, float (*red)[64]) {
+                                                 int blk, int accumulate, float (*red)[64], int fcin, int fcout) {
   constexpr int NW = 16;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int i = blk * 64 + lane;
@@ -885,7 +901,8 @@ __device__ __forceinline__ void slab_cols_scalar(const float* __restrict__ src, 
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) v += red[w][lane];
-    dst[i] = accumulate ? dst[i] + v : v;
+    const int d = fcin > 0 ? slab_frag_dst(i, fcin, fcout) : i;
+    if (d >= 0) dst[d] = accumulate ? dst[d] + v : v;
   }
 }
 
@@ -896,7 +913,7 @@ __device__ __forceinline__ void slab_cols_scalar(const float* __restrict__ src, 
 // fixed-shape LDS tree combines the 128 row lanes, so the order is the same
 // every run.
 __device__ __forceinline__ void slab_cols_vec(const float* __restrict__ src0, float* dst, int len, int nblk, int blk,
-                                              int accumulate, float4 (*red)[8]) {
+                                              int accumulate, float4 (*red)[8], int fcin, int fcout) {
   constexpr int NR = 128;
   const int c4 = threadIdx.x & 7, r = threadIdx.x >> 3;
   const int col = blk * 32 + c4 * 4;
@@ -928,7 +945,15 @@ __device__ __forceinline__ void slab_cols_vec(const float* __restrict__ src0, fl
   if (r == 0 && col < len) {
     const float4 v = red[0][c4];
     float4* d = reinterpret_cast<float4*>(dst + col);
-    if (accumulate) {
+    if (fcin > 0) {
+      // the same sums, each written to its own place (padding dropped)
+      const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int o = slab_frag_dst(col + k, fcin, fcout);
+        if (o >= 0) dst[o] = accumulate ? dst[o] + e[k] : e[k];
+      }
+    } else if (accumulate) {
       const float4 o = *d;
       *d = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
     } else {
@@ -947,9 +972,9 @@ __global__ void __launch_bounds__(1024) slab_reduce_multi_k(SlabTasks T) {
   while (t + 1 < T.ntask && (int)blockIdx.x >= T.start[t + 1]) ++t;
   const int blk = (int)blockIdx.x - T.start[t];
   if (T.vec[t])
-    slab_cols_vec(T.src[t], T.dst[t], T.len[t], T.nblk[t], blk, T.accumulate, red_v);
+    slab_cols_vec(T.src[t], T.dst[t], T.len[t], T.nblk[t], blk, T.accumulate, red_v, T.cin[t], T.cout[t]);
   else
-    slab_cols_scalar(T.src[t], T.dst[t], T.len[t], T.nblk[t], blk, T.accumulate, red_s);
+    slab_cols_scalar(T.src[t], T.dst[t], T.len[t], T.nblk[t], blk, T.accumulate, red_s, T.cin[t], T.cout[t]);
 }
 
 // part[s][n] = sum over rows r in stripe s of X[r][n]
@@ -1239,6 +1264,11 @@ int paig_vel_unpack_add(const float* dX, const float* dpos0, float* dpos, int B,
 
 int paig_slab_reduce_multi(int ntask, const float* const* src, const int* nblk, const int* len, float* const* dst,
                            int accumulate, void* stream) {
+  return paig_slab_reduce_multi_frag(ntask, src, nblk, len, dst, nullptr, nullptr, accumulate, stream);
+}
+
+int paig_slab_reduce_multi_frag(int ntask, const float* const* src, const int* nblk, const int* len,
+                                float* const* dst, const int* cin, const int* cout, int accumulate, void* stream) {
   PAIG_REQUIRE(ntask >= 0 && ntask <= PAIG_MAX_SLAB_TASKS, "slab_reduce_multi: %d tasks", ntask);
   if (ntask == 0) return 0;
   SlabTasks T;
@@ -1250,6 +1280,17 @@ int paig_slab_reduce_multi(int ntask, const float* const* src, const int* nblk, 
     T.nblk[t] = nblk[t];
     T.len[t] = len[t];
     T.vec[t] = len[t] % 4 == 0 && ((uintptr_t)src[t] & 15) == 0 && ((uintptr_t)dst[t] & 15) == 0;
+    T.cin[t] = cin && cout ? cin[t] : 0;
+    T.cout[t] = cin && cout ? cout[t] : 0;
+    if (T.cin[t] > 0) {
+      // rows in accumulator order: the path (hence the summation order) the
+      // layer's plain [Cout*Cin*9 | Cout] rows take, so the sums are the same bits
+      const int ci = T.cin[t], co = T.cout[t];
+      PAIG_REQUIRE(ci % 4 == 0 && co > 0 && co % 8 == 0 && ((uintptr_t)src[t] & 15) == 0 &&
+                       (size_t)len[t] == paig_conv2d_bwd_slab_len(ci, co, 3, 1024),
+                   "slab_reduce_multi: task %d: %d -> %d channels, rows of %d floats", t, ci, co, len[t]);
+      T.vec[t] = (co * ci * 9 + co) % 4 == 0 && ((uintptr_t)dst[t] & 15) == 0;
+    }
     T.start[t] = blocks;
     blocks += cdiv(len[t], T.vec[t] ? 32 : 64);
   }

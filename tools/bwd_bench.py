@@ -3,7 +3,8 @@ paig_conv2d_bwd) at the training step's shapes, HIP events around `reps`
 back-to-back launches; with a -DPAIG_BWD_STAMPS library (PAIG_AB_LIB) also the
 per-tile phase breakdown in shader cycles (s_memtime sums per wave).
 
-usage: python tools/bwd_bench.py [layers=c10,c11] [frames=1000] [reps=20] [mode=split|bf16]
+usage: python tools/bwd_bench.py [layers=c10,c11] [frames=1000] [reps=20] [mode=split|bf16] [rows=plain|frag]
+rows=frag: slab rows in accumulator order (paig_conv2d_bwd flags & 1024).
 Layers: the ShallowUNet's c2..c12 at 32 x 32 (spring), u2 / u3 / u17 of the
 mnist UNet at 64 x 64 (frames default 2560 there).
 """
@@ -29,6 +30,10 @@ LAYERS = {
 }
 PHASES = ["setup", "wait+max+bar", "commit-tail", "issue", "wgrad", "dgrad", "epilogue", "slab", "put_d", "ups_win",
           "ups_bar", "ups_x"]
+# the once-per-block phases split further (stamp slots 13..19; slot 0 / 7 keep the rest of setup / the bias reduction)
+SETUP = {13: "halo0", 14: "wcopy", 15: "addr", 16: "issue0", 17: "xmax", 0: "rest"}
+SLAB = {18: "put_w", 19: "tail", 7: "bias"}
+NST = 20
 
 
 def main():
@@ -36,6 +41,7 @@ def main():
     F0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     reps = int(sys.argv[3]) if len(sys.argv) > 3 else 20
     mode = {"split": 128, "bf16": 256}[sys.argv[4] if len(sys.argv) > 4 else "split"]
+    frag = 1024 if (sys.argv[5] if len(sys.argv) > 5 else "plain") == "frag" else 0
     L = lib()
     stamps = getattr(L.dll, "paig_bwd_stamps_read", None) if hasattr(L.dll, "paig_bwd_stamps_read") else None
     dev = torch.device("cuda:0")
@@ -72,9 +78,10 @@ def main():
         L.paig_conv_wprep(1, (ctypes.c_void_p * 1)(p(w)), (ctypes.c_int * 1)(cout), (ctypes.c_int * 1)(cin),
                           (ctypes.c_int * 1)(3), (ctypes.c_int * 1)(1), (ctypes.c_void_p * 1)(p(wp)), st)
         nmax = 1024
-        slab = torch.empty(nmax * (cout * cin * 9 + cout), device=dev)
+        slen = int(L.paig_conv2d_bwd_slab_len(cin, cout, 3, frag)) if frag else cout * cin * 9 + cout
+        slab = torch.empty(nmax * slen, device=dev)
         nb = ctypes.c_int(0)
-        flags = fl | (64 if kind == "pool" else 0) | (2 if aux_on else 0) | (4 if acc else 0)
+        flags = fl | (64 if kind == "pool" else 0) | (2 if aux_on else 0) | (4 if acc else 0) | frag
 
         def run():
             L.paig_conv2d_bwd(p(x), cin * Hx * Hx, 0, 0, p(dy), cout * H * H, p(dx), cin * Hx * Hx,
@@ -97,13 +104,19 @@ def main():
         if stamps is not None:
             run()
             torch.cuda.synchronize()
-            buf = (ctypes.c_ulonglong * (4096 * 4 * 13))()
+            buf = (ctypes.c_ulonglong * (4096 * 4 * NST))()
             stamps(buf, ctypes.sizeof(buf))
-            t = torch.tensor(list(buf), dtype=torch.float64).view(4096, 4, 13)[:nb.value]
+            t = torch.frombuffer(buf, dtype=torch.int64).to(torch.float64).view(4096, 4, NST)[:nb.value]
             tiles = t[:, :, 12].sum().item()
+            waves = 4 * max(nb.value, 1)
+            blk = [t[:, :, k].sum().item() / waves for k in range(NST)]   # cycles per wave
             per = [t[:, :, k].sum().item() / max(tiles, 1) for k in range(12)]
+            per[0] = sum(blk[k] for k in SETUP) * waves / max(tiles, 1)
+            per[7] = sum(blk[k] for k in SLAB) * waves / max(tiles, 1)
             line += " | cyc/tile " + " ".join(f"{PHASES[k]}={per[k]:.0f}" for k in range(12) if per[k]) + \
-                    f" | loop={sum(per[1:7]) + sum(per[8:]):.0f} tiles/blk={tiles / 4 / max(nb.value, 1):.1f}"
+                    f" | loop={sum(per[1:7]) + sum(per[8:]):.0f} tiles/blk={tiles / 4 / max(nb.value, 1):.1f}" + \
+                    " | cyc/wave setup: " + " ".join(f"{v}={blk[k]:.0f}" for k, v in SETUP.items()) + \
+                    " slab: " + " ".join(f"{v}={blk[k]:.0f}" for k, v in SLAB.items())
         print(line, flush=True)
 
 
