@@ -548,7 +548,9 @@ int paig_decoder_fwd(const float* pos, long long pos_outer, long long pos_inner,
  * which only the first `live` per sequence carry gradient (0: all; the
  * rollout decode's pred_steps, physics_models.py:129-139): the others get
  * dpos = 0 and are not read.  Partial source gradients: one slab row of
- * paig_decoder_slab_len floats per block, paig_decoder_bwd_blocks rows. */
+ * paig_decoder_slab_len floats per block, paig_decoder_bwd_blocks rows (every
+ * _bwd_blocks* / _bwd_scratch* query below and the launch itself read one
+ * plan, dec_bwd_plan in csrc/decoder.hip). */
 /* the physics rollout (paig_rollout_fwd's arguments) and the reconstruction
  * decode (paig_decoder_fwd's; fp32 targets, SSE output required) in one
  * launch: they are independent, and the rollout's one-thread-per-sequence

@@ -2149,16 +2149,81 @@ sigma_grad_k(const double* __restrict__ a, int na, const double* __restrict__ b,
 
 }  // namespace
 
-extern "C" {
+// ---- host side: every decision of a decoder call is made once here.  The
+// sigma operand (DecSigma), the target and loss-weight operands (dec_tview /
+// dec_wsrc, which own their preconditions), the kernels' <T8, LW> choice
+// (dec_t8_lw) and the backward's launch geometry (dec_bwd_plan: what the size
+// queries report is what the launch writes).  The exported variants are thin
+// forwards onto dec_fwd / dec_fwd_rollout / dec_bwd / dec_parts.
 
-// Launch geometry of paig_decoder_bwd: the one-CU-per-block kernel for the
-// headline shapes, the generic kernels otherwise.
-static bool dec_cu_shape(int K, int h, int H) {
-  return H == 2 * h && ((K == 2 && (H == 32 || H == 64)) || (K == 3 && H == 36));
+#define DEC_TRY(call)           \
+  do {                          \
+    if (int rc_ = (call)) return rc_; \
+  } while (0)
+
+// The attention-window scale of one call (physics_models.py:155-162): a host
+// value in [0.5, 2] (no clamping outside), or -- the *_sigma_dev entry points:
+// the learnable scale, which the host never sees -- one double the kernels
+// read from device memory (host is then an unused 1.0).
+struct DecSigma {
+  double host;
+  const double* dev;
+  bool on_dev;
+  static DecSigma of(double sigma) { return {sigma, nullptr, false}; }
+  static DecSigma at(const double* sigma_dev) { return {1.0, sigma_dev, true}; }
+};
+
+static int dec_sigma_check(const char* who, const DecSigma& sg) {
+  PAIG_REQUIRE(!sg.on_dev || sg.dev, "%s: a device sigma is required", who);
+  PAIG_REQUIRE(sg.on_dev || (sg.host >= 0.5 && sg.host <= 2.0), "%s: sigma=%g outside [0.5, 2]", who, sg.host);
+  return 0;
 }
 
-static int dec_live(int F, int grp, int live) {
-  return (grp > 0 && live > 0 && live < grp) ? (F / grp) * live : F;
+static PosView dec_pos(const float* pos, long long outer, long long inner, int grp, const DecSigma& sg) {
+  return PosView{pos, outer, inner, grp, sg.host, (float)sg.host, sg.dev};
+}
+
+// The target forms an entry point takes; dec_tview finishes the view an
+// export filled with its raw arguments.  sse_ok: no forward without an SSE
+// output (the backward passes true).
+enum DecTgtForm { DEC_TGT_F32, DEC_TGT_U8, DEC_TGT_EITHER };
+
+static int dec_tview(const char* who, DecTgtForm form, TView& t, bool sse_ok) {
+  PAIG_REQUIRE(form != DEC_TGT_EITHER || !t.p != !t.p8, "%s: exactly one of the fp32 / byte targets", who);
+  PAIG_REQUIRE(form != DEC_TGT_U8 || t.p8, "%s: byte targets are required", who);
+  PAIG_REQUIRE(!t.ix || t.grp > 0, "%s: a row index needs grouped targets", who);
+  PAIG_REQUIRE(!t.p8 || sse_ok, "%s: byte targets need an SSE output", who);
+  if (!t.p8) t.ix = nullptr;
+  return 0;
+}
+
+// The backward's loss weights: the array (mode 0) or the loss adjoints
+// (mode 1: reconstruction frames, 2: rollout frames, grouped by R).
+static int dec_wsrc(const char* who, WSrc& w, int pos_grp, int F) {
+  PAIG_REQUIRE(w.mode >= 0 && w.mode <= 2 && (w.mode == 0 || (w.B > 0 && w.Te > 0 && w.R > 0)),
+               "%s: loss-weight mode %d", who, w.mode);
+  PAIG_REQUIRE(w.mode != 0 || !w.dt, "%s: loss adjoints given with lw_mode 0", who);
+  PAIG_REQUIRE(w.mode != 2 || (pos_grp == w.R && F % w.R == 0), "%s: rollout weights need frames grouped by R=%d", who,
+               w.R);
+  if (w.mode != 0) w.a = nullptr;
+  return 0;
+}
+
+// fn(T8, LW) with the runtime (byte targets, in-kernel weights) pair as the
+// kernels' template arguments
+template <typename Fn>
+static void dec_t8_lw(bool t8, bool lw, Fn&& fn) {
+  auto with = [&](auto LW) {
+    if (t8) fn(std::true_type{}, LW);
+    else fn(std::false_type{}, LW);
+  };
+  if (lw) with(std::true_type{});
+  else with(std::false_type{});
+}
+
+// The one-CU-per-block kernels' shapes (the generic kernels otherwise).
+static bool dec_cu_shape(int K, int h, int H) {
+  return H == 2 * h && ((K == 2 && (H == 32 || H == 64)) || (K == 3 && H == 36));
 }
 
 // frames per block of the one-CU kernel: >= DEC_FPB_MIN (the slab row of a
@@ -2174,70 +2239,47 @@ static int dec_cu_fpb(int NL) {
   return fpb < fmin ? fmin : fpb;
 }
 
-// The supported attention-window scales (physics_models.py:155-162); no
-// clamping outside them.
-static bool dec_sigma_ok(double sigma) { return sigma >= 0.5 && sigma <= 2.0; }
+// The backward's launch over F frames grouped by grp (0: ungrouped) of which
+// the first `live` per group carry a loss weight (0: all).  The only place
+// this arithmetic exists: the paig_decoder_bwd_blocks* / _bwd_scratch* queries
+// report it and dec_bwd launches it.
+struct DecBwdPlan {
+  bool cu;          // the one-CU kernels, else the generic ones
+  int rows;         // blocks = slab rows
+  int fpb;          // (one-CU) frames per block
+  int live;         // the kernels' live argument
+  size_t scratch;   // (generic) floats of global scratch: the per-frame pixel-gradient image when it does not fit LDS
+  int lds;          // (generic) dynamic LDS bytes
+};
 
-// The backward's path: the one-CU kernels' 5-wide gather tables bound the
-// window for sigma >= 1 (<= 4 / sigma + 1 output indices per source texel and
-// axis); below that (up to 9) the generic kernels take the one-CU shapes too.
-static bool dec_bwd_cu(int K, int h, int H, double sigma) { return dec_cu_shape(K, h, H) && sigma >= 1.0; }
-
-// Slab rows (= blocks) of the backward over F frames grouped by grp
-// (0: ungrouped) of which the first `live` per group are processed (0: all).
-static int dec_gen_blocks(int F) {   // the generic backward's
-  int g = (F + 1) / 2;
-  if (g > 768) g = 768;   // ~3 blocks per CU: latency hiding for the per-frame passes
-  if (g < 1) g = 1;
-  return g;
-}
-
-int paig_decoder_bwd_blocks_sigma(int F, int grp, int live, int K, int h, int H, double sigma) {
-  if (F <= 0) return 1;
-  if (dec_bwd_cu(K, h, H, sigma)) {
-    const int NL = dec_live(F, grp, live);
-    const int g = NL > 0 ? cdiv(NL, dec_cu_fpb(NL)) : 1;
-    return g < 1 ? 1 : g;
+static DecBwdPlan dec_bwd_plan(int F, int grp, int live, int K, int h, int H, const DecSigma& sg) {
+  // The one-CU kernels' 5-wide gather tables bound the window for sigma >= 1
+  // (<= 4 / sigma + 1 output indices per source texel and axis); below that
+  // (up to 9) the generic kernels take the one-CU shapes too, as they do for
+  // a device sigma, which the host cannot choose a kernel by.
+  if (!sg.on_dev && sg.host >= 1.0 && dec_cu_shape(K, h, H)) {
+    // the live frames only; the dead ones of every group are skipped
+    const int NL = (grp > 0 && live > 0 && live < grp) ? (F / grp) * live : F;
+    const int n = NL > 0 ? NL : 1, fpb = dec_cu_fpb(n);
+    return {true, cdiv(n, fpb), fpb, NL == F ? 0 : live, 0, 0};
   }
-  return dec_gen_blocks(F);
+  // generic: every frame is walked (dead ones skipped by their step or zero
+  // weight), two per block up to ~3 blocks per CU (latency hiding for the
+  // per-frame passes)
+  const int g = F <= 0 ? 1 : (F + 1) / 2 < 768 ? (F + 1) / 2 : 768;
+  const size_t src = (size_t)K * h * h * 4, img = (size_t)K * 4 * H * H;
+  if ((src + img) * 4 <= 120 * 1024) return {false, g, 0, live, 0, (int)((src + img) * 4)};
+  return {false, g, 0, live, g * img, (int)(src * 4)};
 }
-
-// a device-resident sigma: always the generic backward (every frame walked)
-int paig_decoder_bwd_blocks_sigma_dev(int F, int K, int h, int H) { return F <= 0 ? 1 : dec_gen_blocks(F); }
-
-int paig_decoder_bwd_blocks(int F, int grp, int live, int K, int h, int H) {
-  return paig_decoder_bwd_blocks_sigma(F, grp, live, K, h, H, 1.0);
-}
-
-size_t paig_decoder_slab_len(int K, int h, int H) { return (size_t)K * h * h * 4 + 3 * (size_t)H * H; }
-
-// Global scratch (floats) needed when the per-frame pixel-gradient image does
-// not fit LDS; 0 when it does.
-static size_t dec_gen_scratch(int F, int K, int h, int H) {
-  size_t lds = ((size_t)K * h * h * 4 + (size_t)K * 4 * H * H) * 4;
-  if (lds <= 120 * 1024) return 0;
-  return (size_t)(F <= 0 ? 1 : dec_gen_blocks(F)) * K * 4 * H * H;
-}
-
-size_t paig_decoder_bwd_scratch_sigma(int F, int K, int h, int H, double sigma) {
-  if (dec_bwd_cu(K, h, H, sigma)) return 0;
-  return dec_gen_scratch(F, K, h, H);
-}
-
-size_t paig_decoder_bwd_scratch_sigma_dev(int F, int K, int h, int H) { return dec_gen_scratch(F, K, h, H); }
-
-size_t paig_decoder_bwd_scratch(int F, int K, int h, int H) { return paig_decoder_bwd_scratch_sigma(F, K, h, H, 1.0); }
-
-}  // extern "C"
 
 static int dec_fwd(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
-                   const float* cont, const float* bg, float* out, long long out_fs, TView t, float* sse, int F, int K,
-                   int h, int H, double sigma, const double* sgp, void* stream) {
-  // sgp: sigma read from device memory by the kernels (`sigma` is then unused)
-  PAIG_REQUIRE(sgp || dec_sigma_ok(sigma), "decoder: sigma=%g outside [0.5, 2]", sigma);
+                   const float* cont, const float* bg, float* out, long long out_fs, DecTgtForm form, TView t,
+                   float* sse, int F, int K, int h, int H, const DecSigma& sg, void* stream) {
+  DEC_TRY(dec_sigma_check("decoder_fwd", sg));
+  DEC_TRY(dec_tview("decoder_fwd", form, t, sse != nullptr));
   if (F <= 0) return 0;
   PAIG_REQUIRE(H == 2 * h, "decoder: H=%d must be 2*tmpl=%d", H, 2 * h);
-  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma, sgp};
+  const PosView pv = dec_pos(pos, pos_outer, pos_inner, pos_grp, sg);
   Src S{tmpl, cont, bg};
   FViewW o{out, out_fs};
   hipStream_t st = (hipStream_t)stream;
@@ -2247,17 +2289,16 @@ static int dec_fwd(const float* pos, long long pos_outer, long long pos_inner, i
   return PAIG_E_UNSUPPORTED;
 }
 
+// dsig (with a device sigma only): dL/dsigma [F]
 static int dec_bwd(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
-                   const float* cont, const float* bg, TView t, WSrc dsse, const float* dout,
+                   const float* cont, const float* bg, DecTgtForm form, TView t, WSrc dsse, const float* dout,
                    long long dout_fs, float* dpos, float* slab, float* scratch, int F, int live, int K, int h, int H,
-                   double sigma, const double* sgp, double* dsig, void* stream) {
-  // sgp: sigma read from device memory (`sigma` unused): the generic kernels,
-  // whose gather window is sized in-kernel; dsig (with sgp only): dL/dsigma [F]
-  PAIG_REQUIRE(sgp || dec_sigma_ok(sigma), "decoder_bwd: sigma=%g outside [0.5, 2]", sigma);
-  PAIG_REQUIRE(sgp || !dsig, "decoder_bwd: dL/dsigma needs a device-resident sigma");
+                   const DecSigma& sg, double* dsig, void* stream) {
+  DEC_TRY(dec_sigma_check("decoder_bwd", sg));
+  PAIG_REQUIRE(sg.on_dev || !dsig, "decoder_bwd: dL/dsigma needs a device-resident sigma");
+  DEC_TRY(dec_tview("decoder_bwd", form, t, true));
+  DEC_TRY(dec_wsrc("decoder_bwd", dsse, pos_grp, F));
   if (F <= 0) return 0;
-  PAIG_REQUIRE(dsse.mode >= 0 && dsse.mode <= 2 && (dsse.mode == 0 || (dsse.B > 0 && dsse.Te > 0 && dsse.R > 0)),
-               "decoder_bwd: loss-weight mode %d", dsse.mode);
   PAIG_REQUIRE(H == 2 * h, "decoder: H=%d must be 2*tmpl=%d", H, 2 * h);
   PAIG_REQUIRE(live >= 0 && (live == 0 || pos_grp > 0), "decoder_bwd: live=%d needs grouped frames (pos_grp=%d)", live,
                pos_grp);
@@ -2269,106 +2310,52 @@ static int dec_bwd(const float* pos, long long pos_outer, long long pos_inner, i
   // generic ones walk them (zero contribution), so both give the same result
   PAIG_REQUIRE(live == 0 || dout == nullptr, "decoder_bwd: live=%d with a dense dL/dout (dead frames would be skipped)",
                live);
-  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma, sgp};
+  const PosView pv = dec_pos(pos, pos_outer, pos_inner, pos_grp, sg);
   Src S{tmpl, cont, bg};
   FView d{dout, dout_fs, 0, 0};
   hipStream_t st = (hipStream_t)stream;
-  if (!sgp && dec_bwd_cu(K, h, H, sigma)) {
-    const int NL = dec_live(F, pos_grp, live);
-    const int fpb = dec_cu_fpb(NL > 0 ? NL : 1);
-    const int g = paig_decoder_bwd_blocks_sigma(F, pos_grp, live, K, h, H, sigma);
-    const int rl = dec_live(F, pos_grp, live) == F ? 0 : live;
-    auto launch = [&](auto t8, auto lw) {
-      constexpr bool T8 = decltype(t8)::value, LW = decltype(lw)::value;
+  const DecBwdPlan pl = dec_bwd_plan(F, pos_grp, live, K, h, H, sg);
+  const bool t8 = t.p8 && dsse.on(), lw = dsse.mode != 0;
+  if (pl.cu) {
+    dec_t8_lw(t8, lw, [&](auto t8c, auto lwc) {
+      constexpr bool T8 = decltype(t8c)::value, LW = decltype(lwc)::value;
       if (K == 2 && H == 64)
-        hipLaunchKernelGGL((dec_bwd_band_k<2, 64, T8, LW>), dim3(g), dim3(DecBand<2, 64>::NT), 0, st, pv, S, t, dsse, d,
-                           dpos, slab, F, rl, fpb);
+        hipLaunchKernelGGL((dec_bwd_band_k<2, 64, T8, LW>), dim3(pl.rows), dim3(DecBand<2, 64>::NT), 0, st, pv, S, t,
+                           dsse, d, dpos, slab, F, pl.live, pl.fpb);
       else if (K == 2)
-        hipLaunchKernelGGL((dec_bwd_cu_k<2, 32, T8, LW>), dim3(g), dim3(DecCu<2, 32>::NT), 0, st, pv, S, t, dsse, d, dpos,
-                           slab, F, rl, fpb);
+        hipLaunchKernelGGL((dec_bwd_cu_k<2, 32, T8, LW>), dim3(pl.rows), dim3(DecCu<2, 32>::NT), 0, st, pv, S, t, dsse, d,
+                           dpos, slab, F, pl.live, pl.fpb);
       else
-        hipLaunchKernelGGL((dec_bwd_cu_k<3, 36, T8, LW>), dim3(g), dim3(DecCu<3, 36>::NT), 0, st, pv, S, t, dsse, d, dpos,
-                           slab, F, rl, fpb);
-    };
-    const bool t8 = t.p8 && dsse.on();
-    if (dsse.mode != 0) {
-      if (t8) launch(std::true_type{}, std::true_type{});
-      else launch(std::false_type{}, std::true_type{});
-    } else {
-      if (t8) launch(std::true_type{}, std::false_type{});
-      else launch(std::false_type{}, std::false_type{});
-    }
+        hipLaunchKernelGGL((dec_bwd_cu_k<3, 36, T8, LW>), dim3(pl.rows), dim3(DecCu<3, 36>::NT), 0, st, pv, S, t, dsse, d,
+                           dpos, slab, F, pl.live, pl.fpb);
+    });
     PAIG_CHECK_LAUNCH();
     return 0;
   }
   // byte targets and in-kernel loss weights: the one-CU shapes (at sigma < 1
   // through the generic kernels)
   PAIG_REQUIRE(!t.p8 || dec_cu_shape(K, h, H), "decoder_bwd: byte targets need the one-CU kernels (K=%d H=%d)", K, H);
-  PAIG_REQUIRE(dsse.mode == 0 || dec_cu_shape(K, h, H),
-               "decoder_bwd: in-kernel loss weights need the one-CU kernels (K=%d H=%d)", K, H);
-  // generic kernels: every frame is walked (dead ones skipped by their step or zero weight)
-  const int g = dec_gen_blocks(F);
-  const bool need_scratch = dec_gen_scratch(F, K, h, H) > 0;
-  PAIG_REQUIRE(!need_scratch || scratch, "decoder_bwd: scratch required");
-  const int lds = (K * h * h * 4 + (need_scratch ? 0 : K * 4 * H * H)) * 4;
-  float* gs = need_scratch ? scratch : nullptr;
+  PAIG_REQUIRE(!lw || dec_cu_shape(K, h, H), "decoder_bwd: in-kernel loss weights need the one-CU kernels (K=%d H=%d)",
+               K, H);
+  PAIG_REQUIRE(!pl.scratch || scratch, "decoder_bwd: scratch required");
+  float* gs = pl.scratch ? scratch : nullptr;
   if (K != 2 && K != 3) {
     paig_set_error("decoder: unsupported n_objs %d", K);
     return PAIG_E_UNSUPPORTED;
   }
-  auto launch = [&](auto t8, auto lw) {
-    constexpr bool T8 = decltype(t8)::value, LW = decltype(lw)::value;
+  dec_t8_lw(t8, lw, [&](auto t8c, auto lwc) {
+    constexpr bool T8 = decltype(t8c)::value, LW = decltype(lwc)::value;
     auto go = [&](auto kern) {
-      if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      hipLaunchKernelGGL(kern, dim3(g), dim3(256), lds, st, pv, S, t, dsse, d, dpos, slab, gs, dsig, F, live, h, H);
+      if (pl.lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+      hipLaunchKernelGGL(kern, dim3(pl.rows), dim3(256), pl.lds, st, pv, S, t, dsse, d, dpos, slab, gs, dsig, F, pl.live,
+                         h, H);
     };
     if (K == 2) go(dec_bwd_k<2, T8, LW>);
     else go(dec_bwd_k<3, T8, LW>);
-  };
-  const bool t8 = t.p8 && dsse.on();
-  if (dsse.mode != 0) {
-    if (t8) launch(std::true_type{}, std::true_type{});
-    else launch(std::false_type{}, std::true_type{});
-  } else {
-    if (t8) launch(std::true_type{}, std::false_type{});
-    else launch(std::false_type{}, std::false_type{});
-  }
+  });
   PAIG_CHECK_LAUNCH();
   return 0;
-}
-
-extern "C" {
-
-// The *_sigma entry points take the attention-window scale sigma =
-// np.exp(np.log(log_sig)) of physics_models.py:160-162 (theta0 = theta4 =
-// sigma in fp64, theta2 / theta5 scaled by fl32(sigma) in fp32, :163-167), in
-// [0.5, 2]; the entry points without it mean sigma = 1.
-int paig_decoder_fwd_sigma(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
-                           const float* cont, const float* bg, float* out, long long out_fs, const float* tgt,
-                           long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H,
-                           double sigma, void* stream) {
-  return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
-                 TView{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, sigma, nullptr, stream);
-}
-
-// The *_sigma_dev entry points: the *_sigma ones with sigma read by the
-// kernels from device memory (const double* sigma_dev, one element: the
-// learnable scale of physics_models.py:155-161, which the host never sees).
-int paig_decoder_fwd_sigma_dev(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
-                               const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
-                               const float* tgt, long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F,
-                               int K, int h, int H, const double* sigma_dev, void* stream) {
-  PAIG_REQUIRE(sigma_dev, "decoder_fwd_sigma_dev: a device sigma is required");
-  return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
-                 TView{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, 1.0, sigma_dev, stream);
-}
-
-int paig_decoder_fwd(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
-                     const float* cont, const float* bg, float* out, long long out_fs, const float* tgt,
-                     long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H,
-                     void* stream) {
-  return paig_decoder_fwd_sigma(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs, tgt, tgt_fs, tgt_grp,
-                                tgt_gs, sse, F, K, h, H, 1.0, stream);
 }
 
 // The rollout (paig_rollout_fwd's arguments) and the reconstruction decode
@@ -2379,16 +2366,16 @@ static int dec_fwd_rollout(int cell, const float* pos0, long long pos0_ld, const
                            const double* p0, const double* p1, float* pvs, int B, int D, int R, const float* pos,
                            long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl, const float* cont,
                            const float* bg, float* out, long long out_fs, const float* tgt, long long tgt_fs,
-                           int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H, double sigma,
-                           const double* sgp, void* stream) {
-  PAIG_REQUIRE(sgp || dec_sigma_ok(sigma), "decoder_fwd_rollout: sigma=%g outside [0.5, 2]", sigma);
+                           int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H, const DecSigma& sg,
+                           void* stream) {
+  DEC_TRY(dec_sigma_check("decoder_fwd_rollout", sg));
   PAIG_REQUIRE(B > 0 && F > 0 && R > 0, "decoder_fwd_rollout: B=%d F=%d R=%d", B, F, R);
   PAIG_REQUIRE(cell == 1 || (p0 && p1), "decoder_fwd_rollout: physics params required");
   PAIG_REQUIRE(H == 2 * h && sse && tgt, "decoder_fwd_rollout: H=%d tmpl=%d, targets and an SSE output required", H, h);
   const bool al = ((uintptr_t)out | (uintptr_t)bg | (uintptr_t)tgt) % 16 == 0 && out_fs % 4 == 0 && tgt_fs % 4 == 0 &&
                   tgt_gs % 4 == 0;
   PAIG_REQUIRE(al, "decoder_fwd_rollout: 16-byte aligned frames required");
-  PosView pv{pos, pos_outer, pos_inner, pos_grp, sigma, (float)sigma, sgp};
+  const PosView pv = dec_pos(pos, pos_outer, pos_inner, pos_grp, sg);
   Src S{tmpl, cont, bg};
   FViewW o{out, out_fs};
   TView t{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp};
@@ -2420,88 +2407,118 @@ static int dec_fwd_rollout(int cell, const float* pos0, long long pos0_ld, const
   return 0;
 }
 
-int paig_decoder_fwd_rollout_sigma(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
-                                   const double* p0, const double* p1, float* pvs, int B, int D, int R,
-                                   const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
-                                   const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
-                                   const float* tgt, long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F,
-                                   int K, int h, int H, double sigma, void* stream) {
-  return dec_fwd_rollout(cell, pos0, pos0_ld, vel0, dt, p0, p1, pvs, B, D, R, pos, pos_outer, pos_inner, pos_grp, tmpl,
-                         cont, bg, out, out_fs, tgt, tgt_fs, tgt_grp, tgt_gs, sse, F, K, h, H, sigma, nullptr, stream);
+static int dec_parts(const float* pos, long long pos_inner, const float* tmpl, const float* cont, const float* bg,
+                     float* contents, float* masks, int F, int K, int h, int H, const DecSigma& sg, void* stream) {
+  DEC_TRY(dec_sigma_check("decoder_parts", sg));
+  if (F <= 0) return 0;
+  PAIG_REQUIRE(H == 2 * h && H <= MAXH, "decoder_parts: H=%d must be 2*tmpl=%d (<= %d)", H, 2 * h, MAXH);
+  const PosView pv = dec_pos(pos, 0, pos_inner, 0, sg);
+  Src S{tmpl, cont, bg};
+  hipStream_t st = (hipStream_t)stream;
+  const int g = F < 2048 ? F : 2048;
+  const int lds = (K * h * h * 4) * 4;
+  if (K == 2) hipLaunchKernelGGL((dec_parts_k<2>), dim3(g), dim3(256), lds, st, pv, S, contents, masks, F, h, H);
+  else if (K == 3) hipLaunchKernelGGL((dec_parts_k<3>), dim3(g), dim3(256), lds, st, pv, S, contents, masks, F, h, H);
+  else {
+    paig_set_error("decoder_parts: unsupported n_objs %d", K);
+    return PAIG_E_UNSUPPORTED;
+  }
+  PAIG_CHECK_LAUNCH();
+  return 0;
 }
 
-int paig_decoder_fwd_rollout_sigma_dev(int cell, const float* pos0, long long pos0_ld, const float* vel0,
-                                       const float* dt, const double* p0, const double* p1, float* pvs, int B, int D,
-                                       int R, const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
-                                       const float* tmpl, const float* cont, const float* bg, float* out,
-                                       long long out_fs, const float* tgt, long long tgt_fs, int tgt_grp,
-                                       long long tgt_gs, float* sse, int F, int K, int h, int H,
-                                       const double* sigma_dev, void* stream) {
-  PAIG_REQUIRE(sigma_dev, "decoder_fwd_rollout_sigma_dev: a device sigma is required");
-  return dec_fwd_rollout(cell, pos0, pos0_ld, vel0, dt, p0, p1, pvs, B, D, R, pos, pos_outer, pos_inner, pos_grp, tmpl,
-                         cont, bg, out, out_fs, tgt, tgt_fs, tgt_grp, tgt_gs, sse, F, K, h, H, 1.0, sigma_dev, stream);
+// ---- the C ABI.  Per operation: the *_sigma entry point takes the window
+// scale (double sigma, in [0.5, 2]: theta0 = theta4 = sigma in fp64, theta2 /
+// theta5 scaled by fl32(sigma) in fp32, physics_models.py:160-167), the
+// *_sigma_dev one reads it from device memory (const double* sigma_dev, one
+// element), and the one without a suffix means sigma = 1.
+#define DEC_POS_P const float *pos, long long pos_outer, long long pos_inner, int pos_grp
+#define DEC_POS pos, pos_outer, pos_inner, pos_grp
+#define DEC_SRC_P const float *tmpl, const float *cont, const float *bg
+#define DEC_SRC tmpl, cont, bg
+#define DEC_TGT_P long long tgt_fs, int tgt_grp, long long tgt_gs
+#define DEC_F32 DEC_TGT_F32, TView{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp}
+#define DEC_U8 DEC_TGT_U8, TView{nullptr, tgt, tgt_idx, tgt_fs, tgt_gs, tgt_grp}
+#define DEC_DIMS_P int F, int K, int h, int H
+#define DEC_DIMS F, K, h, H
+
+extern "C" {
+
+// Slab rows (= blocks) and global scratch (floats; 0 when the per-frame
+// pixel-gradient image fits LDS) of the backward: dec_bwd_plan.  A device
+// sigma: always the generic backward (every frame walked).
+int paig_decoder_bwd_blocks_sigma(int F, int grp, int live, int K, int h, int H, double sigma) {
+  return dec_bwd_plan(F, grp, live, K, h, H, DecSigma::of(sigma)).rows;
+}
+int paig_decoder_bwd_blocks_sigma_dev(DEC_DIMS_P) { return dec_bwd_plan(F, 0, 0, K, h, H, DecSigma::at(nullptr)).rows; }
+int paig_decoder_bwd_blocks(int F, int grp, int live, int K, int h, int H) {
+  return paig_decoder_bwd_blocks_sigma(F, grp, live, K, h, H, 1.0);
+}
+size_t paig_decoder_bwd_scratch_sigma(DEC_DIMS_P, double sigma) {
+  return dec_bwd_plan(F, 0, 0, K, h, H, DecSigma::of(sigma)).scratch;
+}
+size_t paig_decoder_bwd_scratch_sigma_dev(DEC_DIMS_P) {
+  return dec_bwd_plan(F, 0, 0, K, h, H, DecSigma::at(nullptr)).scratch;
+}
+size_t paig_decoder_bwd_scratch(DEC_DIMS_P) { return paig_decoder_bwd_scratch_sigma(DEC_DIMS, 1.0); }
+size_t paig_decoder_slab_len(int K, int h, int H) { return (size_t)K * h * h * 4 + 3 * (size_t)H * H; }
+
+int paig_decoder_fwd_sigma(DEC_POS_P, DEC_SRC_P, float* out, long long out_fs, const float* tgt, DEC_TGT_P, float* sse,
+                           DEC_DIMS_P, double sigma, void* stream) {
+  return dec_fwd(DEC_POS, DEC_SRC, out, out_fs, DEC_F32, sse, DEC_DIMS, DecSigma::of(sigma), stream);
+}
+int paig_decoder_fwd_sigma_dev(DEC_POS_P, DEC_SRC_P, float* out, long long out_fs, const float* tgt, DEC_TGT_P,
+                               float* sse, DEC_DIMS_P, const double* sigma_dev, void* stream) {
+  return dec_fwd(DEC_POS, DEC_SRC, out, out_fs, DEC_F32, sse, DEC_DIMS, DecSigma::at(sigma_dev), stream);
+}
+int paig_decoder_fwd(DEC_POS_P, DEC_SRC_P, float* out, long long out_fs, const float* tgt, DEC_TGT_P, float* sse,
+                     DEC_DIMS_P, void* stream) {
+  return dec_fwd(DEC_POS, DEC_SRC, out, out_fs, DEC_F32, sse, DEC_DIMS, DecSigma::of(1.0), stream);
 }
 
-int paig_decoder_fwd_rollout(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
-                             const double* p0, const double* p1, float* pvs, int B, int D, int R, const float* pos,
-                             long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
-                             const float* cont, const float* bg, float* out, long long out_fs, const float* tgt,
-                             long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H,
-                             void* stream) {
-  return paig_decoder_fwd_rollout_sigma(cell, pos0, pos0_ld, vel0, dt, p0, p1, pvs, B, D, R, pos, pos_outer, pos_inner,
-                                        pos_grp, tmpl, cont, bg, out, out_fs, tgt, tgt_fs, tgt_grp, tgt_gs, sse, F, K, h,
-                                        H, 1.0, stream);
+// byte targets (the dataset's rows behind tgt_idx) and an SSE output
+int paig_decoder_fwd_t8_sigma(DEC_POS_P, DEC_SRC_P, float* out, long long out_fs, const unsigned char* tgt,
+                              const long long* tgt_idx, DEC_TGT_P, float* sse, DEC_DIMS_P, double sigma, void* stream) {
+  return dec_fwd(DEC_POS, DEC_SRC, out, out_fs, DEC_U8, sse, DEC_DIMS, DecSigma::of(sigma), stream);
 }
-
-int paig_decoder_fwd_t8_sigma(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
-                              const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
-                              const unsigned char* tgt, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
-                              long long tgt_gs, float* sse, int F, int K, int h, int H, double sigma, void* stream) {
-  PAIG_REQUIRE(tgt && sse, "decoder_fwd_t8: byte targets and an SSE output are required");
-  PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_fwd_t8: a row index needs grouped targets");
-  return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
-                 TView{nullptr, tgt, tgt_idx, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, sigma, nullptr, stream);
-}
-
-int paig_decoder_fwd_t8_sigma_dev(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
-                                  const float* tmpl, const float* cont, const float* bg, float* out, long long out_fs,
-                                  const unsigned char* tgt, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
-                                  long long tgt_gs, float* sse, int F, int K, int h, int H, const double* sigma_dev,
+int paig_decoder_fwd_t8_sigma_dev(DEC_POS_P, DEC_SRC_P, float* out, long long out_fs, const unsigned char* tgt,
+                                  const long long* tgt_idx, DEC_TGT_P, float* sse, DEC_DIMS_P, const double* sigma_dev,
                                   void* stream) {
-  PAIG_REQUIRE(tgt && sse, "decoder_fwd_t8: byte targets and an SSE output are required");
-  PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_fwd_t8: a row index needs grouped targets");
-  PAIG_REQUIRE(sigma_dev, "decoder_fwd_t8_sigma_dev: a device sigma is required");
-  return dec_fwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs,
-                 TView{nullptr, tgt, tgt_idx, tgt_fs, tgt_gs, tgt_grp}, sse, F, K, h, H, 1.0, sigma_dev, stream);
+  return dec_fwd(DEC_POS, DEC_SRC, out, out_fs, DEC_U8, sse, DEC_DIMS, DecSigma::at(sigma_dev), stream);
+}
+int paig_decoder_fwd_t8(DEC_POS_P, DEC_SRC_P, float* out, long long out_fs, const unsigned char* tgt,
+                        const long long* tgt_idx, DEC_TGT_P, float* sse, DEC_DIMS_P, void* stream) {
+  return dec_fwd(DEC_POS, DEC_SRC, out, out_fs, DEC_U8, sse, DEC_DIMS, DecSigma::of(1.0), stream);
 }
 
-int paig_decoder_fwd_t8(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
-                        const float* cont, const float* bg, float* out, long long out_fs, const unsigned char* tgt,
-                        const long long* tgt_idx, long long tgt_fs, int tgt_grp, long long tgt_gs, float* sse, int F, int K, int h, int H,
-                        void* stream) {
-  return paig_decoder_fwd_t8_sigma(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, out, out_fs, tgt, tgt_idx, tgt_fs,
-                                   tgt_grp, tgt_gs, sse, F, K, h, H, 1.0, stream);
-}
+#define DEC_ROLL_P                                                                                                  \
+  int cell, const float *pos0, long long pos0_ld, const float *vel0, const float *dt, const double *p0,             \
+      const double *p1, float *pvs, int B, int D, int R, DEC_POS_P, DEC_SRC_P, float *out, long long out_fs,        \
+      const float *tgt, DEC_TGT_P, float *sse, DEC_DIMS_P
+#define DEC_ROLL                                                                                                     \
+  cell, pos0, pos0_ld, vel0, dt, p0, p1, pvs, B, D, R, DEC_POS, DEC_SRC, out, out_fs, tgt, tgt_fs, tgt_grp, tgt_gs, \
+      sse, DEC_DIMS
 
-int paig_decoder_bwd(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
-                     const float* cont, const float* bg, const float* tgt, long long tgt_fs, int tgt_grp,
-                     long long tgt_gs, const float* dsse, const float* dout, long long dout_fs, float* dpos,
-                     float* slab, float* scratch, int F, int live, int K, int h, int H, void* stream) {
-  return dec_bwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, TView{tgt, nullptr, nullptr, tgt_fs, tgt_gs, tgt_grp},
-                 WSrc{dsse, nullptr, nullptr, nullptr, 0.f, 0, 0, 0, 0, 0}, dout, dout_fs, dpos, slab, scratch, F, live, K, h,
-                 H, 1.0, nullptr, nullptr, stream);
+int paig_decoder_fwd_rollout_sigma(DEC_ROLL_P, double sigma, void* stream) {
+  return dec_fwd_rollout(DEC_ROLL, DecSigma::of(sigma), stream);
 }
+int paig_decoder_fwd_rollout_sigma_dev(DEC_ROLL_P, const double* sigma_dev, void* stream) {
+  return dec_fwd_rollout(DEC_ROLL, DecSigma::at(sigma_dev), stream);
+}
+int paig_decoder_fwd_rollout(DEC_ROLL_P, void* stream) { return dec_fwd_rollout(DEC_ROLL, DecSigma::of(1.0), stream); }
 
-int paig_decoder_bwd_t8(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
-                        const float* cont, const float* bg, const unsigned char* tgt, const long long* tgt_idx,
-                        long long tgt_fs, int tgt_grp,
-                        long long tgt_gs, const float* dsse, const float* dout, long long dout_fs, float* dpos,
-                        float* slab, float* scratch, int F, int live, int K, int h, int H, void* stream) {
-  PAIG_REQUIRE(tgt, "decoder_bwd_t8: byte targets are required");
-  PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_bwd_t8: a row index needs grouped targets");
-  return dec_bwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, TView{nullptr, tgt, tgt_idx, tgt_fs, tgt_gs, tgt_grp},
-                 WSrc{dsse, nullptr, nullptr, nullptr, 0.f, 0, 0, 0, 0, 0}, dout, dout_fs, dpos, slab, scratch, F, live, K, h,
-                 H, 1.0, nullptr, nullptr, stream);
+// The backward with the weight array dsse: fp32 targets, or (_t8) bytes
+#define DEC_BWD_OUT_P const float *dout, long long dout_fs, float *dpos, float *slab, float *scratch
+#define DEC_BWD_OUT dout, dout_fs, dpos, slab, scratch
+#define DEC_NO_LW WSrc{dsse, nullptr, nullptr, nullptr, 0.f, 0, 0, 0, 0, 0}
+
+int paig_decoder_bwd(DEC_POS_P, DEC_SRC_P, const float* tgt, DEC_TGT_P, const float* dsse, DEC_BWD_OUT_P, int F,
+                     int live, int K, int h, int H, void* stream) {
+  return dec_bwd(DEC_POS, DEC_SRC, DEC_F32, DEC_NO_LW, DEC_BWD_OUT, F, live, K, h, H, DecSigma::of(1.0), nullptr, stream);
+}
+int paig_decoder_bwd_t8(DEC_POS_P, DEC_SRC_P, const unsigned char* tgt, const long long* tgt_idx, DEC_TGT_P,
+                        const float* dsse, DEC_BWD_OUT_P, int F, int live, int K, int h, int H, void* stream) {
+  return dec_bwd(DEC_POS, DEC_SRC, DEC_U8, DEC_NO_LW, DEC_BWD_OUT, F, live, K, h, H, DecSigma::of(1.0), nullptr, stream);
 }
 
 // The backward with either target form (tgt fp32, or tgt8 + tgt_idx bytes:
@@ -2509,44 +2526,36 @@ int paig_decoder_bwd_t8(const float* pos, long long pos_outer, long long pos_inn
 // formed in-kernel from the loss adjoints dt / de / dr (lw_mode 1:
 // reconstruction frames, 2: rollout frames; paig_loss_bwd's values, so no
 // weight arrays and no paig_loss_bwd launch).  lw_mode != 0: the one-CU shapes.
-// Slab rows / scratch: paig_decoder_bwd_blocks_sigma / _bwd_scratch_sigma.
-int paig_decoder_bwd_ex_sigma(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
-                              const float* tmpl, const float* cont, const float* bg, const float* tgt,
-                              const unsigned char* tgt8, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
-                              long long tgt_gs, const float* dsse, int lw_mode, const float* dt, const float* de,
-                              const float* dr, float ae, int lB, int lTe, int lR, int lpred, const float* dout,
-                              long long dout_fs, float* dpos, float* slab, float* scratch, int F, int live, int K,
-                              int h, int H, double sigma, void* stream) {
-  PAIG_REQUIRE(!tgt != !tgt8, "decoder_bwd_ex: exactly one of the fp32 / byte targets");
-  PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_bwd_ex: a row index needs grouped targets");
-  PAIG_REQUIRE(lw_mode != 0 || !dt, "decoder_bwd_ex: loss adjoints given with lw_mode 0");
-  PAIG_REQUIRE(lw_mode != 2 || (pos_grp == lR && F % lR == 0), "decoder_bwd_ex: rollout weights need frames grouped by R=%d",
-               lR);
-  return dec_bwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, TView{tgt, tgt8, tgt8 ? tgt_idx : nullptr, tgt_fs, tgt_gs, tgt_grp},
-                 WSrc{lw_mode ? nullptr : dsse, dt, de, dr, ae, lB, lTe, lR, lpred, lw_mode}, dout, dout_fs, dpos, slab,
-                 scratch, F, live, K, h, H, sigma, nullptr, nullptr, stream);
-}
+// _sigma_dev: always the generic kernels, and dsig (nullable) [F]: every
+// frame's dL/dsigma in fp64, 0.0 for the frames the launch skips (dead or
+// weightless).  Slab rows / scratch: the matching _bwd_blocks* / _bwd_scratch*.
+#define DEC_EX_P                                                                                                   \
+  DEC_POS_P, DEC_SRC_P, const float *tgt, const unsigned char *tgt8, const long long *tgt_idx, DEC_TGT_P,          \
+      const float *dsse, int lw_mode, const float *dt, const float *de, const float *dr, float ae, int lB, int lTe, \
+      int lR, int lpred, DEC_BWD_OUT_P, int F, int live, int K, int h, int H
+#define DEC_EX                                                                                                  \
+  DEC_POS, DEC_SRC, DEC_TGT_EITHER, TView{tgt, tgt8, tgt_idx, tgt_fs, tgt_gs, tgt_grp},                         \
+      WSrc{dsse, dt, de, dr, ae, lB, lTe, lR, lpred, lw_mode}, DEC_BWD_OUT, F, live, K, h, H
 
-// paig_decoder_bwd_ex_sigma with sigma in device memory: always the generic
-// kernels (slab rows / scratch: paig_decoder_bwd_blocks_sigma_dev /
-// _bwd_scratch_sigma_dev), and dsig (nullable) [F]: every frame's dL/dsigma in
-// fp64, 0.0 for the frames the launch skips (dead or weightless).
-int paig_decoder_bwd_ex_sigma_dev(const float* pos, long long pos_outer, long long pos_inner, int pos_grp,
-                                  const float* tmpl, const float* cont, const float* bg, const float* tgt,
-                                  const unsigned char* tgt8, const long long* tgt_idx, long long tgt_fs, int tgt_grp,
-                                  long long tgt_gs, const float* dsse, int lw_mode, const float* dt, const float* de,
-                                  const float* dr, float ae, int lB, int lTe, int lR, int lpred, const float* dout,
-                                  long long dout_fs, float* dpos, float* slab, float* scratch, int F, int live, int K,
-                                  int h, int H, const double* sigma_dev, double* dsig, void* stream) {
-  PAIG_REQUIRE(!tgt != !tgt8, "decoder_bwd_ex: exactly one of the fp32 / byte targets");
-  PAIG_REQUIRE(!tgt_idx || tgt_grp > 0, "decoder_bwd_ex: a row index needs grouped targets");
-  PAIG_REQUIRE(lw_mode != 0 || !dt, "decoder_bwd_ex: loss adjoints given with lw_mode 0");
-  PAIG_REQUIRE(lw_mode != 2 || (pos_grp == lR && F % lR == 0), "decoder_bwd_ex: rollout weights need frames grouped by R=%d",
-               lR);
-  PAIG_REQUIRE(sigma_dev, "decoder_bwd_ex_sigma_dev: a device sigma is required");
-  return dec_bwd(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, TView{tgt, tgt8, tgt8 ? tgt_idx : nullptr, tgt_fs, tgt_gs, tgt_grp},
-                 WSrc{lw_mode ? nullptr : dsse, dt, de, dr, ae, lB, lTe, lR, lpred, lw_mode}, dout, dout_fs, dpos, slab,
-                 scratch, F, live, K, h, H, 1.0, sigma_dev, dsig, stream);
+int paig_decoder_bwd_ex_sigma(DEC_EX_P, double sigma, void* stream) {
+  return dec_bwd(DEC_EX, DecSigma::of(sigma), nullptr, stream);
+}
+int paig_decoder_bwd_ex_sigma_dev(DEC_EX_P, const double* sigma_dev, double* dsig, void* stream) {
+  return dec_bwd(DEC_EX, DecSigma::at(sigma_dev), dsig, stream);
+}
+int paig_decoder_bwd_ex(DEC_EX_P, void* stream) { return dec_bwd(DEC_EX, DecSigma::of(1.0), nullptr, stream); }
+
+int paig_decoder_parts_sigma(const float* pos, long long pos_inner, DEC_SRC_P, float* contents, float* masks, DEC_DIMS_P,
+                             double sigma, void* stream) {
+  return dec_parts(pos, pos_inner, DEC_SRC, contents, masks, DEC_DIMS, DecSigma::of(sigma), stream);
+}
+int paig_decoder_parts_sigma_dev(const float* pos, long long pos_inner, DEC_SRC_P, float* contents, float* masks,
+                                 DEC_DIMS_P, const double* sigma_dev, void* stream) {
+  return dec_parts(pos, pos_inner, DEC_SRC, contents, masks, DEC_DIMS, DecSigma::at(sigma_dev), stream);
+}
+int paig_decoder_parts(const float* pos, long long pos_inner, DEC_SRC_P, float* contents, float* masks, DEC_DIMS_P,
+                       void* stream) {
+  return dec_parts(pos, pos_inner, DEC_SRC, contents, masks, DEC_DIMS, DecSigma::of(1.0), stream);
 }
 
 int paig_sigma_from_u(const float* u, double* sigma_dev, void* stream) {
@@ -2563,17 +2572,6 @@ int paig_sigma_grad(const double* dsig_a, int na, const double* dsig_b, int nb, 
                      accumulate);
   PAIG_CHECK_LAUNCH();
   return 0;
-}
-
-int paig_decoder_bwd_ex(const float* pos, long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,
-                        const float* cont, const float* bg, const float* tgt, const unsigned char* tgt8,
-                        const long long* tgt_idx, long long tgt_fs, int tgt_grp, long long tgt_gs, const float* dsse,
-                        int lw_mode, const float* dt, const float* de, const float* dr, float ae, int lB, int lTe,
-                        int lR, int lpred, const float* dout, long long dout_fs, float* dpos, float* slab,
-                        float* scratch, int F, int live, int K, int h, int H, void* stream) {
-  return paig_decoder_bwd_ex_sigma(pos, pos_outer, pos_inner, pos_grp, tmpl, cont, bg, tgt, tgt8, tgt_idx, tgt_fs, tgt_grp,
-                                   tgt_gs, dsse, lw_mode, dt, de, dr, ae, lB, lTe, lR, lpred, dout, dout_fs, dpos, slab,
-                                   scratch, F, live, K, h, H, 1.0, stream);
 }
 
 }  // extern "C"
@@ -2603,44 +2601,6 @@ static int stn_bwd(const float* U, const T* theta, const float* dout, float* dU,
 
 extern "C" {
 
-static int dec_parts(const float* pos, long long pos_inner, const float* tmpl, const float* cont, const float* bg,
-                     float* contents, float* masks, int F, int K, int h, int H, double sigma, const double* sgp,
-                     void* stream) {
-  PAIG_REQUIRE(sgp || dec_sigma_ok(sigma), "decoder_parts: sigma=%g outside [0.5, 2]", sigma);
-  if (F <= 0) return 0;
-  PAIG_REQUIRE(H == 2 * h && H <= MAXH, "decoder_parts: H=%d must be 2*tmpl=%d (<= %d)", H, 2 * h, MAXH);
-  PosView pv{pos, 0, pos_inner, 0, sigma, (float)sigma, sgp};
-  Src S{tmpl, cont, bg};
-  hipStream_t st = (hipStream_t)stream;
-  const int g = F < 2048 ? F : 2048;
-  const int lds = (K * h * h * 4) * 4;
-  if (K == 2) hipLaunchKernelGGL((dec_parts_k<2>), dim3(g), dim3(256), lds, st, pv, S, contents, masks, F, h, H);
-  else if (K == 3) hipLaunchKernelGGL((dec_parts_k<3>), dim3(g), dim3(256), lds, st, pv, S, contents, masks, F, h, H);
-  else {
-    paig_set_error("decoder_parts: unsupported n_objs %d", K);
-    return PAIG_E_UNSUPPORTED;
-  }
-  PAIG_CHECK_LAUNCH();
-  return 0;
-}
-
-int paig_decoder_parts_sigma(const float* pos, long long pos_inner, const float* tmpl, const float* cont,
-                             const float* bg, float* contents, float* masks, int F, int K, int h, int H, double sigma,
-                             void* stream) {
-  return dec_parts(pos, pos_inner, tmpl, cont, bg, contents, masks, F, K, h, H, sigma, nullptr, stream);
-}
-
-int paig_decoder_parts_sigma_dev(const float* pos, long long pos_inner, const float* tmpl, const float* cont,
-                                 const float* bg, float* contents, float* masks, int F, int K, int h, int H,
-                                 const double* sigma_dev, void* stream) {
-  PAIG_REQUIRE(sigma_dev, "decoder_parts_sigma_dev: a device sigma is required");
-  return dec_parts(pos, pos_inner, tmpl, cont, bg, contents, masks, F, K, h, H, 1.0, sigma_dev, stream);
-}
-
-int paig_decoder_parts(const float* pos, long long pos_inner, const float* tmpl, const float* cont, const float* bg,
-                       float* contents, float* masks, int F, int K, int h, int H, void* stream) {
-  return paig_decoder_parts_sigma(pos, pos_inner, tmpl, cont, bg, contents, masks, F, K, h, H, 1.0, stream);
-}
 
 int paig_stn_fwd(const float* U, const float* theta, float* out, int N, int C, int Hi, int Wi, int Ho, int Wo,
                  void* stream) {

@@ -26,6 +26,7 @@ from typing import NamedTuple
 import torch
 
 from ._lib import PaigError, lib, ptr, stream_handle, require_device
+from .decoder_ops import DecoderOps, Sigma, Targets
 
 # The U-Net plans (ShallowUNet blocks.py:240-308, UNet :106-237: buffers,
 # ops, which upsamples / pools fuse into which convs, the backward's
@@ -265,11 +266,11 @@ class StepState:
     need_saved: bool = True     # new_state: a backward may follow; _unet_forward (else the inference workspace)
     sw: Switches = None         # new_state: the forward's A/B switches; every stage
     x_view: tuple = None        # new_state: the encoder's frames (pointer, stride, group, group stride)
-    sigma: float = 1.0          # forward: the decoders' window scale (model.decoder_sigma()); forward, backward
-    sigma_dev: object = None    # forward (learn_sigma, else None): the model's one-double device sigma, written by
-    #                             paig_sigma_from_u at the start of the forward; the decoders' forward and backward
-    tb: int = 0                 # forward: 1 = the rollout targets are dataset bytes; backward
-    tgt_roll: tuple = None      # forward: the rollout decoders' target view; backward
+    sigma: Sigma = None         # forward: the decoders' window scale: model.decoder_sigma(), or (learn_sigma) the
+    #                             model's one-double device sigma, written by paig_sigma_from_u at the start of the
+    #                             forward; the decoders' forward and backward
+    tgt_rec: Targets = None     # forward: the reconstruction decoders' targets (the encoder's frames); backward
+    tgt_roll: Targets = None    # forward: the rollout decoders' targets (x's frames or the dataset's bytes); backward
     src: dict = None            # forward: VFN buffers {name: (hidden, raw, post-sigmoid or None)}; backward
     Xv: object = None           # forward: velocity encoder input rows; backward
     v1: object = None           # forward: velocity MLP hidden 1; backward
@@ -318,7 +319,7 @@ class Engine:
         self.L = lib()
         self.probe = None
         self.last_masked_objs = None
-        self.last_sigma = 1.0           # the last forward's decoder window scale (StepState.sigma)
+        self.last_sigma = 1.0           # the last forward's decoder window scale (StepState.sigma.value)
         self.last_loss_handoff = None   # the last forward's loss-weight hand-off (physics_models._LossHandoff)
         # called once per backward when the early gradient bucket is final
         # (FlatParams.allreduce_early by default; bench.py splits its HIP graph here)
@@ -458,6 +459,19 @@ class Engine:
         return (lay.cell, ptr(S.enc_pos) + (lay.ins - 1) * lay.D * 4, lay.Te * lay.D, ptr(S.vel0), ptr(dt), ptr(p0),
                 ptr(p1), ptr(S.pvs), lay.B, lay.D, lay.R)
 
+    def _decoder_ops(self, S):
+        """The decoder calls of this forward's sigma and VFN sources."""
+        lay = S.lay
+        return DecoderOps(self.L, lay.K, lay.h, lay.H, S.sigma, (ptr(S.src["var_net_template"][1]),
+                                                                 ptr(S.src["var_net_content"][1]),
+                                                                 ptr(S.src["var_net_background"][2])))
+
+    @staticmethod
+    def _roll_pos(S):
+        """The rollout frames' position view: steps 1..R of every sequence of pvs."""
+        D, R = S.lay.D, S.lay.R
+        return (ptr(S.pvs) + 2 * D * 4, (R + 1) * 2 * D, 2 * D, R)
+
     def _head_bwd_prefix(self, S, denc, dh2, hslab):
         """(h2, h3, d enc_pos, W3, d h2, slab, F, K, 200, H/2) of every paig_head*_bwd* entry point."""
         lay = S.lay
@@ -489,16 +503,13 @@ class Engine:
         learn = getattr(model, "learn_sigma", False)
         # log_sig is read at every forward, as in the reference; the learnable
         # scale is never read by the host (decoder_sigma() would synchronise)
-        sigma = 1.0 if learn else model.decoder_sigma()
         S = self.new_state(lay, x, need_saved)
-        S.sigma = sigma
+        S.sigma = Sigma(model.sigma_buffer() if learn else model.decoder_sigma())
         dev, ws, sw = S.dev, S.ws, S.sw
         st = stream_handle(dev)
         if learn:   # sigma from u, on the step's stream: captured with the graph
-            S.sigma_dev = model.sigma_buffer()
-            L.paig_sigma_from_u(ptr(self.p("decoder_sigma_u")), ptr(S.sigma_dev), st)
-        self.last_sigma = S.sigma_dev if learn else sigma
-        sg_arg, sg_sfx = (ptr(S.sigma_dev), "_sigma_dev") if learn else (S.sigma, "_sigma")
+            L.paig_sigma_from_u(ptr(self.p("decoder_sigma_u")), S.sigma.arg, st)
+        self.last_sigma = S.sigma.value
         K, F, HW, H, h, D = lay.K, lay.F, lay.HW, lay.H, lay.h, lay.D
 
         # ---- VariableFromNetwork sources (once per step, Q12; only the decoders read them)
@@ -513,10 +524,11 @@ class Engine:
         # gather writes as fp32 in either case: read there (no row lookup)
         bt = self.byte_targets
         if bt is not None and bt.covers(x, lay):
-            S.tb = 1
-            S.tgt_roll = (bt.base + lay.ins * lay.frame, bt.idx_ptr, T * lay.frame, lay.R, lay.frame)
+            S.tgt_roll = Targets.dataset_bytes(bt.base + lay.ins * lay.frame, bt.idx_ptr, T * lay.frame, lay.R,
+                                               lay.frame)
         else:
-            S.tgt_roll = (ptr(x) + lay.ins * lay.frame * 4, T * lay.frame, lay.R, lay.frame)
+            S.tgt_roll = Targets.frames(ptr(x) + lay.ins * lay.frame * 4, T * lay.frame, lay.R, lay.frame)
+        S.tgt_rec = Targets.frames(*S.x_view)
         self._encoder_forward(S, st)
         enc_pos = S.enc_pos
 
@@ -536,8 +548,7 @@ class Engine:
         S.pvs = _empty(B * (lay.R + 1) * 2 * D, dev)
         roll = self._rollout_args(S)
         vel_act = (ptr(S.Xv), ptr(S.v1), ptr(S.v2), ptr(S.vel0))
-        dec = (ptr(enc_pos), 0, 2 * K, 0, ptr(tmpl), ptr(cont), ptr(bgp), ptr(recons), lay.frame, *S.x_view,
-               ptr(sse_rec), F, K, h, H, sg_arg)
+        dec = self._decoder_ops(S)
         # velocity MLP + VFN sources in one launch (independent); then the
         # rollout and the reconstruction decode in one launch
         fuse_vfn = S.vel0 is not None and not lay.alt_vel and sw.fuse_vfn
@@ -556,18 +567,14 @@ class Engine:
             L.paig_vfn_fwd_multi(*self._vfn_fwd_args(S), st)
         # reconstruction decode (all B*Te frames, SSE vs input fused)
         with self._p("dec_fwd:recon+rollout" if merge_roll else "dec_fwd:recon", 0, self._dec_bytes(F, lay)):
-            if merge_roll:
-                getattr(L, "paig_decoder_fwd_rollout" + sg_sfx)(*roll, *dec, st)
-            else:
-                getattr(L, "paig_decoder_fwd" + sg_sfx)(*dec, st)
+            dec.fwd((ptr(enc_pos), 0, 2 * K, 0), ptr(recons), lay.frame, S.tgt_rec, ptr(sse_rec), F, st,
+                    roll=roll if merge_roll else None)
 
         # ---- rollout decode (all B*R frames in one launch, SSE vs input[:, ins:])
         out = _empty(B * lay.R * lay.frame, dev)
         sse_roll = _empty(B * lay.R, dev)
-        dec_fwd = getattr(L, ("paig_decoder_fwd_t8" if S.tb else "paig_decoder_fwd") + sg_sfx)
-        with self._p("dec_fwd:rollout", 0, self._dec_bytes(B * lay.R, lay, S.tb or 4)):
-            dec_fwd(ptr(S.pvs) + 2 * D * 4, (lay.R + 1) * 2 * D, 2 * D, lay.R, ptr(tmpl), ptr(cont), ptr(bgp),
-                    ptr(out), lay.frame, *S.tgt_roll, ptr(sse_roll), B * lay.R, K, h, H, sg_arg, st)
+        with self._p("dec_fwd:rollout", 0, self._dec_bytes(B * lay.R, lay, S.tgt_roll.value_bytes)):
+            dec.fwd(self._roll_pos(S), ptr(out), lay.frame, S.tgt_roll, ptr(sse_roll), B * lay.R, st)
 
         masks, objs = S.masks, S.objs
         res = {
@@ -776,29 +783,6 @@ class Engine:
         return dt, None, None
 
     # -- backward --------------------------------------------------------
-    def _decoder_bwd(self, S, pos, po, pi, pg, tgt, dsse, lw, dout, dpos, slab_p, scr, nfr, live, st, dsig=None):
-        """paig_decoder_bwd_ex_sigma (the forward's sigma) over nfr frames at positions (pos, po, pi, pg):
-        fp32 (4-tuple) or byte (5-tuple) targets tgt; lw: in-kernel loss
-        weights (mode, LossAdjoints) or None (dsse read).  Learnable sigma
-        (S.sigma_dev): paig_decoder_bwd_ex_sigma_dev, which also writes the
-        frames' dL/dsigma to dsig (a device address)."""
-        lay = S.lay
-        tf, t8, ti = (tgt[0], None, None) if len(tgt) == 4 else (None, tgt[0], tgt[1])
-        fs, grp, gs = tgt[-3:]
-        if lw is not None:
-            mode, adj = lw
-            lwa = (mode, ptr(adj.dt), ptr(adj.de), ptr(adj.dr), float(adj.ae), adj.B, adj.Te, adj.R, adj.pred)
-            dsse = None
-        else:
-            lwa = (0, None, None, None, 0.0, 0, 0, 0, 0)
-        args = (pos, po, pi, pg, ptr(S.src["var_net_template"][1]), ptr(S.src["var_net_content"][1]),
-                ptr(S.src["var_net_background"][2]), tf, t8, ti, fs, grp, gs, ptr(dsse), *lwa, ptr(dout), lay.frame,
-                dpos, slab_p, scr, nfr, live, lay.K, lay.h, lay.H)
-        if S.sigma_dev is not None:
-            self.L.paig_decoder_bwd_ex_sigma_dev(*args, ptr(S.sigma_dev), dsig, st)
-        else:
-            self.L.paig_decoder_bwd_ex_sigma(*args, S.sigma, st)
-
     def backward(self, S, d_sse_rec=None, d_sse_roll=None, d_out=None, d_recons=None, d_enc_pos=None, d_pvs=None,
                  roll_live=0, lossw=None):
         """Writes every live parameter gradient into the model's flat grad buffer.
@@ -826,26 +810,17 @@ class Engine:
             d_recons = d_recons.contiguous()
 
         # ---- buffers of the whole decoder / rollout / velocity backward
-        slab_len = int(L.paig_decoder_slab_len(K, h, H))
+        dec = self._decoder_ops(S)
+        slab_len = dec.slab_len
         roll_live = roll_live if (d_out is None and 0 < roll_live < R) else 0
-        learn = S.sigma_dev is not None
+        learn = S.sigma.has_grad
         dsig_rec = dsig_roll = None
-        if learn:
-            # the generic backward (the host cannot choose a kernel by a sigma
-            # it does not know); every frame's dL/dsigma, both decoders' arrays
-            nb_rec = L.paig_decoder_bwd_blocks_sigma_dev(F, K, h, H)
-            nb_roll = L.paig_decoder_bwd_blocks_sigma_dev(B * R, K, h, H)
-            scr_n = max(L.paig_decoder_bwd_scratch_sigma_dev(F, K, h, H),
-                        L.paig_decoder_bwd_scratch_sigma_dev(B * R, K, h, H))
+        if learn:   # every frame's dL/dsigma, both decoders' arrays
             dsig = _empty(F + B * R, dev, torch.float64)
             dsig_rec, dsig_roll = ptr(dsig), ptr(dsig) + F * 8
-        else:
-            nb_rec = L.paig_decoder_bwd_blocks_sigma(F, 0, 0, K, h, H, S.sigma)
-            nb_roll = L.paig_decoder_bwd_blocks_sigma(B * R, R, roll_live, K, h, H, S.sigma)
-            scr_n = max(L.paig_decoder_bwd_scratch_sigma(F, K, h, H, S.sigma),
-                        L.paig_decoder_bwd_scratch_sigma(B * R, K, h, H, S.sigma))
+        (nb_rec, scr_rec), (nb_roll, scr_roll) = dec.bwd_sizes(F), dec.bwd_sizes(B * R, R, roll_live)
         slab = _empty((nb_rec + nb_roll) * slab_len, dev)
-        scratch = _empty(scr_n, dev) if scr_n else None
+        scratch = _empty(max(scr_rec, scr_roll), dev) if max(scr_rec, scr_roll) else None
         denc = _empty(F * D, dev)   # d enc_pos [B][Te][D]
         dpos_roll = _empty(B * R * D, dev)
         dsrc = _empty(slab_len, dev)
@@ -866,10 +841,10 @@ class Engine:
 
         # ---- rollout-frame decoder backward: d rollout positions + partial source grads
         live_frames = B * roll_live if roll_live else B * R
-        with self._p("dec_bwd:rollout", 0, self._dec_bwd_bytes(live_frames, B * R, lay, d_out is not None, S.tb or 4)):
-            self._decoder_bwd(S, ptr(S.pvs) + 2 * D * 4, (R + 1) * 2 * D, 2 * D, R, S.tgt_roll, d_sse_roll,
-                              lossw.get("roll"), d_out, ptr(dpos_roll), ptr(slab) + nb_rec * slab_len * 4,
-                              ptr(scratch), B * R, roll_live, st, dsig_roll)
+        with self._p("dec_bwd:rollout", 0,
+                     self._dec_bwd_bytes(live_frames, B * R, lay, d_out is not None, S.tgt_roll.value_bytes)):
+            dec.bwd(self._roll_pos(S), S.tgt_roll, ptr(d_sse_roll), lossw.get("roll"), ptr(d_out), lay.frame,
+                    ptr(dpos_roll), ptr(slab) + nb_rec * slab_len * 4, ptr(scratch), B * R, roll_live, st, dsig_roll)
 
         # ---- rollout adjoint -> d pos0, d vel0, physics params; velocity encoder backward
         prm = self.cell_params(lay)
@@ -894,8 +869,8 @@ class Engine:
 
         # ---- reconstruction decoder backward: d enc_pos + partial source grads
         with self._p("dec_bwd:recon", 0, self._dec_bwd_bytes(F, F, lay, d_recons is not None)):
-            self._decoder_bwd(S, ptr(S.enc_pos), 0, 2 * K, 0, S.x_view, d_sse_rec, lossw.get("rec"), d_recons,
-                              ptr(denc), ptr(slab), ptr(scratch), F, 0, st, dsig_rec)
+            dec.bwd((ptr(S.enc_pos), 0, 2 * K, 0), S.tgt_rec, ptr(d_sse_rec), lossw.get("rec"), ptr(d_recons), lay.frame,
+                    ptr(denc), ptr(slab), ptr(scratch), F, 0, st, dsig_rec)
         if learn:   # both decoders' dL/dsigma -> d loss / du (chain rule), into u's flat gradient slot
             L.paig_sigma_grad(dsig_rec, F, dsig_roll, B * R, ptr(self.p("decoder_sigma_u")),
                               ptr(self.g("decoder_sigma_u")), 0, st)

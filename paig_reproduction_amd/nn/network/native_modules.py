@@ -23,6 +23,7 @@ import ctypes
 import torch
 
 from paig_reproduction_amd._lib import lib, ptr, stream_handle, require_device
+from paig_reproduction_amd.decoder_ops import DecoderOps, Sigma, Targets
 from paig_reproduction_amd.flat import deposit_grad
 
 
@@ -261,6 +262,13 @@ def batch_transformer(U, thetas, out_size):
 
 
 # ----------------------------------------------------------- decoder ------
+def decoder_ops(model, srcs, sigma):
+    """The decoder calls over model._decoder_sources' result at one call's
+    sigma (a float, or the learnable scale's device tensor)."""
+    K, H = model.n_objs, model.conv_input_shape[1]
+    return DecoderOps(lib(), K, H // 2, H, Sigma(sigma), (ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"])))
+
+
 class _STDecoder(torch.autograd.Function):
     """conv_st_decoder (physics_models.py:151-199) with its three
     VariableFromNetwork sources: positions [N, 2K] -> frames [N, 3, H, W]."""
@@ -272,62 +280,46 @@ class _STDecoder(torch.autograd.Function):
         st = stream_handle(dev)
         L = lib()
         K, H = model.n_objs, model.conv_input_shape[1]
-        h = H // 2
         N = pos.shape[0]
         srcs = model._decoder_sources(dev, st)
         out = torch.empty(N, 3, H, H, device=dev)
-        dec = (ptr(pos), 0, 2 * K, 0, ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"]), ptr(out), 3 * H * H, None,
-               0, 0, 0, None, N, K, h, H)
         if getattr(model, "learn_sigma", False):
             # the learned scale, formed on the device from u (no host read); a
             # buffer of this call's own, so its backward sees its forward's value
             sigma = torch.empty(1, device=dev, dtype=torch.float64)
             L.paig_sigma_from_u(ptr(model.decoder_sigma_u), ptr(sigma), st)
-            L.paig_decoder_fwd_sigma_dev(*dec, ptr(sigma), st)
         else:
             sigma = model.decoder_sigma()   # this call's: the backward uses its own forward's value
-            L.paig_decoder_fwd_sigma(*dec, sigma, st)
-        ctx.model, ctx.pos, ctx.srcs, ctx.sigma = model, pos, srcs, sigma
+        dec = decoder_ops(model, srcs, sigma)
+        dec.fwd((ptr(pos), 0, 2 * K, 0), ptr(out), 3 * H * H, Targets.none(), None, N, st)
+        ctx.model, ctx.pos, ctx.srcs, ctx.dec = model, pos, srcs, dec   # (dec points into srcs)
         object.__setattr__(model, "_last_decoder_sigma", sigma)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        model, pos, srcs, sigma = ctx.model, ctx.pos, ctx.srcs, ctx.sigma
+        model, pos, srcs, dec = ctx.model, ctx.pos, ctx.srcs, ctx.dec
         dev = pos.device
         st = stream_handle(dev)
         L = lib()
         K, H = model.n_objs, model.conv_input_shape[1]
-        h = H // 2
         N = pos.shape[0]
         dout = dout.float().contiguous()
-        slab_len = int(L.paig_decoder_slab_len(K, h, H))
-        learn = torch.is_tensor(sigma)
-        if learn:
-            nb = L.paig_decoder_bwd_blocks_sigma_dev(N, K, h, H)
-            scr_n = L.paig_decoder_bwd_scratch_sigma_dev(N, K, h, H)
-        else:
-            nb = L.paig_decoder_bwd_blocks_sigma(N, 0, 0, K, h, H, sigma)
-            scr_n = L.paig_decoder_bwd_scratch_sigma(N, K, h, H, sigma)
+        slab_len = dec.slab_len
+        nb, scr_n = dec.bwd_sizes(N)
         slab = torch.empty(nb * slab_len, device=dev)
         scratch = torch.empty(scr_n, device=dev) if scr_n else None
         dpos = torch.empty(N, 2 * K, device=dev)
+        # u's gradient through the step's own kernels: per-frame dL/dsigma,
+        # then the reduction + chain rule, deposited with torch semantics
+        dsig = torch.empty(N, device=dev, dtype=torch.float64) if dec.sigma.has_grad else None
         # no target frames: the SSE weight is null and dL/dout comes dense
-        # (the target pointer must still address N valid frames; dout does)
-        args = (ptr(pos), 0, 2 * K, 0, ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"]), ptr(dout), None, None,
-                3 * H * H, 0, 0, None, 0, None, None, None, 0.0, 0, 0, 0, 0, ptr(dout), 3 * H * H, ptr(dpos), ptr(slab),
-                ptr(scratch), N, 0, K, h, H)
-        if learn:
-            # u's gradient through the step's own kernels: per-frame dL/dsigma,
-            # then the reduction + chain rule, deposited with torch semantics
-            from paig_reproduction_amd.flat import deposit_grad
-            dsig = torch.empty(N, device=dev, dtype=torch.float64)
-            L.paig_decoder_bwd_ex_sigma_dev(*args, ptr(sigma), ptr(dsig), st)
+        dec.bwd((ptr(pos), 0, 2 * K, 0), Targets.none(), None, None, ptr(dout), 3 * H * H, ptr(dpos), ptr(slab),
+                ptr(scratch), N, 0, st, ptr(dsig))
+        if dsig is not None:
             gu = torch.empty((), device=dev)
             L.paig_sigma_grad(ptr(dsig), N, None, 0, ptr(model.decoder_sigma_u), ptr(gu), 0, st)
             deposit_grad(model.decoder_sigma_u, gu)
-        else:
-            L.paig_decoder_bwd_ex_sigma(*args, sigma, st)
         dsrc = torch.empty(slab_len, device=dev)
         L.paig_slab_reduce(ptr(slab), nb, slab_len, slab_len, ptr(dsrc), 0, st)
         model._decoder_sources_backward(srcs, dsrc, st)

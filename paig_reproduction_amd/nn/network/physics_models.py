@@ -566,9 +566,8 @@ class PhysicsNet(BaseNetTorch):
         dev = pos.device
         cont = torch.empty(K + 1, N, 3, H, H, device=dev)
         masks = torch.empty(K + 1, N, 3, H, H, device=dev)
-        parts = lib().paig_decoder_parts_sigma_dev if torch.is_tensor(sigma) else lib().paig_decoder_parts_sigma
-        parts(ptr(pos), inner, ptr(srcs["tmpl"]), ptr(srcs["cont"]), ptr(srcs["bg"]), ptr(cont), ptr(masks), N, K,
-              H // 2, H, ptr(sigma) if torch.is_tensor(sigma) else sigma, stream_handle(dev))
+        from paig_reproduction_amd.nn.network.native_modules import decoder_ops
+        decoder_ops(self, srcs, sigma).parts(ptr(pos), inner, ptr(cont), ptr(masks), N, stream_handle(dev))
         res = ([cont[k] for k in range(K + 1)], tuple(masks[k] for k in range(K + 1)))
         object.__setattr__(self, "_parts_cache", (self._parts, res))
         return res

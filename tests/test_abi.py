@@ -71,6 +71,84 @@ def test_library_loads_and_exports_every_symbol():
         assert L.paig_unet_buffer(net, 10, H, 2, 128, 1 | 4, 1, hb) == -1
 
 
+# The decoder backward's size queries, recorded from the library before its
+# launch plan became one function (csrc/decoder.hip dec_bwd_plan), with
+# PAIG_DEC_FPB_MIN unset.  (K, h, H) -> (F, grp, live) -> (blocks, blocks_sigma
+# at QUERY_SIGMAS, blocks_sigma_dev, scratch, scratch_sigma at QUERY_SIGMAS,
+# scratch_sigma_dev); F a multiple of grp where grouped.
+QUERY_SIGMAS = (0.5, 0.99, 1.0, 2.0)
+QUERY_TABLE = {
+    (2, 16, 32): {
+        (0, 0, 0): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (0, 4, 2): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (0, 46, 6): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (1, 0, 0): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (5, 0, 0): (2, (3, 3, 2, 2), 3, 0, (0, 0, 0, 0), 0),
+        (12, 0, 0): (4, (6, 6, 4, 4), 6, 0, (0, 0, 0, 0), 0),
+        (12, 4, 2): (2, (6, 6, 2, 2), 6, 0, (0, 0, 0, 0), 0),
+        (4600, 0, 0): (256, (768, 768, 256, 256), 768, 0, (0, 0, 0, 0), 0),
+        (4600, 4, 2): (256, (768, 768, 256, 256), 768, 0, (0, 0, 0, 0), 0),
+        (4600, 46, 6): (200, (768, 768, 200, 200), 768, 0, (0, 0, 0, 0), 0),
+    },
+    (3, 18, 36): {
+        (0, 0, 0): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (0, 4, 2): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (0, 46, 6): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (1, 0, 0): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (5, 0, 0): (2, (3, 3, 2, 2), 3, 0, (0, 0, 0, 0), 0),
+        (12, 0, 0): (4, (6, 6, 4, 4), 6, 0, (0, 0, 0, 0), 0),
+        (12, 4, 2): (2, (6, 6, 2, 2), 6, 0, (0, 0, 0, 0), 0),
+        (4600, 0, 0): (256, (768, 768, 256, 256), 768, 0, (0, 0, 0, 0), 0),
+        (4600, 4, 2): (256, (768, 768, 256, 256), 768, 0, (0, 0, 0, 0), 0),
+        (4600, 46, 6): (200, (768, 768, 200, 200), 768, 0, (0, 0, 0, 0), 0),
+    },
+    (2, 32, 64): {   # the pixel-gradient image does not fit LDS: global scratch on the generic path
+        (0, 0, 0): (1, (1, 1, 1, 1), 1, 0, (32768, 32768, 0, 0), 32768),
+        (0, 4, 2): (1, (1, 1, 1, 1), 1, 0, (32768, 32768, 0, 0), 32768),
+        (0, 46, 6): (1, (1, 1, 1, 1), 1, 0, (32768, 32768, 0, 0), 32768),
+        (1, 0, 0): (1, (1, 1, 1, 1), 1, 0, (32768, 32768, 0, 0), 32768),
+        (5, 0, 0): (2, (3, 3, 2, 2), 3, 0, (98304, 98304, 0, 0), 98304),
+        (12, 0, 0): (4, (6, 6, 4, 4), 6, 0, (196608, 196608, 0, 0), 196608),
+        (12, 4, 2): (2, (6, 6, 2, 2), 6, 0, (196608, 196608, 0, 0), 196608),
+        (4600, 0, 0): (256, (768, 768, 256, 256), 768, 0, (25165824, 25165824, 0, 0), 25165824),
+        (4600, 4, 2): (256, (768, 768, 256, 256), 768, 0, (25165824, 25165824, 0, 0), 25165824),
+        (4600, 46, 6): (200, (768, 768, 200, 200), 768, 0, (25165824, 25165824, 0, 0), 25165824),
+    },
+    (2, 20, 40): {   # not a one-CU shape: the generic kernels at every sigma
+        (0, 0, 0): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (0, 4, 2): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (0, 46, 6): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (1, 0, 0): (1, (1, 1, 1, 1), 1, 0, (0, 0, 0, 0), 0),
+        (5, 0, 0): (3, (3, 3, 3, 3), 3, 0, (0, 0, 0, 0), 0),
+        (12, 0, 0): (6, (6, 6, 6, 6), 6, 0, (0, 0, 0, 0), 0),
+        (12, 4, 2): (6, (6, 6, 6, 6), 6, 0, (0, 0, 0, 0), 0),
+        (4600, 0, 0): (768, (768, 768, 768, 768), 768, 0, (0, 0, 0, 0), 0),
+        (4600, 4, 2): (768, (768, 768, 768, 768), 768, 0, (0, 0, 0, 0), 0),
+        (4600, 46, 6): (768, (768, 768, 768, 768), 768, 0, (0, 0, 0, 0), 0),
+    },
+}
+
+
+@pytest.mark.parametrize("shape", list(QUERY_TABLE))
+def test_decoder_bwd_size_queries_match_the_recorded_table(shape):
+    L = _lib.lib()
+    K, h, H = shape
+    # the one-CU path's rows depend on PAIG_DEC_FPB_MIN: recorded with it unset
+    fpb_env = "PAIG_DEC_FPB_MIN" in os.environ
+    one_cu = shape in ((2, 16, 32), (3, 18, 36), (2, 32, 64))
+    for (F, grp, live), (nb, nb_s, nb_dev, scr, scr_s, scr_dev) in QUERY_TABLE[shape].items():
+        case = (shape, F, grp, live)
+        if not (one_cu and fpb_env):
+            assert L.paig_decoder_bwd_blocks(F, grp, live, K, h, H) == nb, case
+        for sigma, want in zip(QUERY_SIGMAS, nb_s):
+            if not (one_cu and sigma >= 1.0 and fpb_env):
+                assert L.paig_decoder_bwd_blocks_sigma(F, grp, live, K, h, H, sigma) == want, (case, sigma)
+        assert L.paig_decoder_bwd_blocks_sigma_dev(F, K, h, H) == nb_dev, case
+        assert L.paig_decoder_bwd_scratch(F, K, h, H) == scr, case
+        assert tuple(L.paig_decoder_bwd_scratch_sigma(F, K, h, H, s) for s in QUERY_SIGMAS) == scr_s, case
+        assert L.paig_decoder_bwd_scratch_sigma_dev(F, K, h, H) == scr_dev, case
+
+
 def test_product_path_refuses_cpu_tensors():
     import torch
     with pytest.raises(_lib.PaigError):

@@ -14,7 +14,8 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from paig_reproduction_amd._lib import lib  # noqa: E402
+from paig_reproduction_amd._lib import lib, ptr  # noqa: E402
+from paig_reproduction_amd.decoder_ops import DecoderOps, Sigma, Targets  # noqa: E402
 
 # name: (K, H, B, R or 0 (ungrouped: B frames), live steps)
 CASES = {
@@ -56,44 +57,27 @@ def main():
         sse = torch.empty(F, device=dev)
         if R:
             pv = (pos.data_ptr() + 2 * K * 4, (R + 1) * 2 * K, 2 * K, R)
-            tv = (x.data_ptr() + 4 * fr * 4, T * fr, R, fr)
+            tv = Targets.frames(x.data_ptr() + 4 * fr * 4, T * fr, R, fr)
         else:
             pv = (pos.data_ptr(), 0, 2 * K, 0)
-            tv = (x.data_ptr(), fr, 0, 0)
-        slab_len = int(L.paig_decoder_slab_len(K, h, H))
-        if sigma is None:
-            nb, scr = L.paig_decoder_bwd_blocks(F, R, live, K, h, H), L.paig_decoder_bwd_scratch(F, K, h, H)
-        else:
-            nb = L.paig_decoder_bwd_blocks_sigma(F, R, live, K, h, H, sigma)
-            scr = L.paig_decoder_bwd_scratch_sigma(F, K, h, H, sigma)
+            tv = Targets.frames(x.data_ptr(), fr, 0, 0)
+        # without --sigma: sigma = 1 (what the entry points without a suffix mean)
+        dec = DecoderOps(L, K, h, H, Sigma(1.0 if sigma is None else sigma), (ptr(tmpl), ptr(cont), ptr(bg)))
+        slab_len = dec.slab_len
+        nb, scr = dec.bwd_sizes(F, R, live)
         slab = torch.empty(nb * slab_len, device=dev)
         scratch = torch.empty(scr, device=dev) if scr else None
         dpos = torch.empty(F * 2 * K, device=dev)
 
-        def fwd_s():
-            L.paig_decoder_fwd_sigma(*pv, tmpl.data_ptr(), cont.data_ptr(), bg.data_ptr(), out.data_ptr(), fr, *tv,
-                                     sse.data_ptr(), F, K, h, H, sigma, st)
-
-        def bwd_s():
-            L.paig_decoder_bwd_ex_sigma(*pv, tmpl.data_ptr(), cont.data_ptr(), bg.data_ptr(), tv[0], None, None, *tv[1:],
-                                        w.data_ptr(), 0, None, None, None, 0.0, 0, 0, 0, 0, None, fr, dpos.data_ptr(),
-                                        slab.data_ptr(), None if scratch is None else scratch.data_ptr(), F,
-                                        live if R else 0, K, h, H, sigma, st)
-
         def fwd():
-            L.paig_decoder_fwd(*pv, tmpl.data_ptr(), cont.data_ptr(), bg.data_ptr(), out.data_ptr(), fr, *tv,
-                               sse.data_ptr(), F, K, h, H, st)
+            dec.fwd(pv, ptr(out), fr, tv, ptr(sse), F, st)
 
         def bwd():
-            rc = L.paig_decoder_bwd(*pv, tmpl.data_ptr(), cont.data_ptr(), bg.data_ptr(), *tv, w.data_ptr(), None,
-                                    fr, dpos.data_ptr(), slab.data_ptr(),
-                                    None if scratch is None else scratch.data_ptr(), F, live if R else 0, K, h, H,
-                                    st)
-            assert rc == 0, L.paig_last_error()
+            dec.bwd(pv, tv, ptr(w), None, None, fr, ptr(dpos), ptr(slab), ptr(scratch), F, live if R else 0, st)
 
         nlive = B * live if R else F
-        for kind, fn, nbytes in (("fwd", fwd if sigma is None else fwd_s, 2 * F * fr * 4),
-                                 ("bwd", bwd if sigma is None else bwd_s, nlive * fr * 4 + F * 2 * K * 4 + slab_len * 4)):
+        for kind, fn, nbytes in (("fwd", fwd, 2 * F * fr * 4),
+                                 ("bwd", bwd, nlive * fr * 4 + F * 2 * K * 4 + slab_len * 4)):
             for _ in range(3):
                 fn()
             torch.cuda.synchronize()
