@@ -33,6 +33,16 @@
 // data gradient of a tile is complete in the tile, so its epilogue takes the
 // exponents back out exactly.  PM 2: bf16 hi only, unscaled (BASELINE config
 // #2).
+//
+// Prologue (once per block).  Split arithmetic (sbwd_early): the xmax slots,
+// the weight header and the prepared weight image are loaded into registers at
+// kernel entry, the first tile's prefetch is issued behind them as soon as
+// its addressing is formed, and the halo zeroing, the weight fragments' LDS
+// stores and the wave's xmax partial follow: one memory round trip.  The
+// xmax partials (sxm) are published by the first tile's loop-top barrier and
+// read after it; the prologue has no barrier of its own.  bf16, and the one
+// shape without a register to spare, walk halos, weights, addressing,
+// prefetch and xmax (two barriers) one after the other.
 #include "split_common.h"
 
 #include <stdlib.h>
@@ -53,6 +63,9 @@
 #ifndef PAIG_BWD_AUXP
 #define PAIG_BWD_AUXP 1   // A/B builds: 0 = the epilogue loads its ReLU' mask when it needs it
 #endif
+#ifndef PAIG_BWD_EARLY
+#define PAIG_BWD_EARLY 1   // A/B builds: 0 = the prologue's loads in three dependent round trips (sbwd_early)
+#endif
 
 // Diagnostic build only (-DPAIG_BWD_STAMPS, tools/bwd_bench.py): per wave,
 // s_memtime cycle sums of the tile loop's phases (0 setup, 1 prefetch wait +
@@ -61,6 +74,10 @@
 // halo, 10 its barrier, 11 the upsampled X staging), the tile count (12) and
 // the once-per-block phases split further (setup: 13 halo zeroing, 14 weight
 // image copy, 15 addressing, 16 first issue, 17 xmax reduction, 0 the rest;
+// with the entry loads (sbwd_early): 0 also their issue, 16 also the wait
+// for the first tile's dY and with it for the entry loads (the compiler
+// places it there), 14 the fragments' LDS stores, 17 the register and wave
+// maximum (the block maximum is formed in the first tile, phase 1);
 // slab: 18 the whole N-tiles' stores, 19 the tail N-tile reduction + stores, 7
 // the bias reduction), stored by lane 0 (vector stores)
 #ifdef PAIG_BWD_STAMPS
@@ -158,6 +175,19 @@ constexpr bool sbwd_fragrows(int CIN, int COUT, int H, int PM, bool PF) {
   return !(CIN == 8 && COUT == 8 && H == 36 && PM == 0 && !PF);
 }
 
+// the shapes whose prologue issues its xmax, weight-header and weight-image
+// loads at kernel entry, ahead of the first tile's prefetch (split arithmetic
+// only: bf16 has neither an xmax nor a prepared image).  The image entries
+// wait in registers (2 x 4 x ceil(NS NTD / 4) VGPRs) beside the first tile's
+// prefetch, before any accumulator is live.  Not 3bp's plain 8 -> 8 at
+// 36 x 36, which has no register to spare at three blocks per CU (measured:
+// -Rpass-analysis=kernel-resource-usage shows 6 spilled VGPRs with the early
+// loads, none without): it keeps the three round trips
+constexpr bool sbwd_early(int CIN, int COUT, int H, int PM, bool UPS, bool PF) {
+  if (CIN == 8 && COUT == 8 && H == 36 && !PF) return false;
+  return PAIG_BWD_EARLY && PM == 0;
+}
+
 // 4 waves split the weight-gradient N-tiles (each wave owns every 4th one
 // over all pixels: no cross-wave reduction); the data gradient's M-tiles of
 // 16 pixels are split over the waves as in the dgrad kernel
@@ -221,6 +251,7 @@ struct SBwdCfg {
   static constexpr int LDS = (IMGD + WIMG) * 2 * NIMG + XREG + (UPS ? UPW * 4 : 0);
   static constexpr bool VEC4 = W % 4 == 0;
   static constexpr bool HOIST = sbwd_hoist(CIN, COUT, H, PM, PF);
+  static constexpr bool EARLY = sbwd_early(CIN, COUT, H, PM, UPS, PF);
   // X prefetched a tile ahead where its registers are cheap (else loaded
   // when staged)
   static constexpr bool XPIPE = !UPS && NLX * 8 <= 32;
@@ -280,24 +311,60 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
   float* Sl = reinterpret_cast<float*>(reinterpret_cast<char*>(Xh) + C::XREG);   // UPS window
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4;
   __shared__ float smax[4];
+  // the waves' xmax partials (C::EARLY): written once per launch, before the
+  // first tile's loop-top barrier, and read after it
+  __shared__ float sxm[4];
 #ifdef PAIG_BWD_STAMPS
   unsigned long long st_acc[20] = {}, st_last = __builtin_amdgcn_s_memtime(), st_n = 0;
 #endif
 
+  // ---- scales (PM 0): X per launch (ecx), dY per tile (ecd), the
+  // data-gradient weights per output channel (ewn)
+  int ecx = PAIG_A_EXP, ecd = PM == 0 && PAIG_SCALE_MODE < 2 ? 100 : 0;
+  float xsc = 1.f, dsc = __builtin_amdgcn_ldexpf(1.f, ecd);
+  float rmax = 0.f;   // range guard (fixed X scale without xmax slots)
+  int ewn[NTD];
+#pragma unroll
+  for (int nt = 0; nt < NTD; ++nt) ewn[nt] = 0;
+
+  // ---- C::EARLY: everything the prologue reads from memory is issued here,
+  // into registers, oldest first: the xmax slots, the weight header and the
+  // weight image (paig_conv_wprep's dgrad image).  The first tile's prefetch
+  // follows once its addressing is formed, and the halo zeroing, the weight
+  // fragments' LDS stores and the xmax reduction run under that latency: one
+  // memory round trip where there were three (vmcnt retires in order, so the
+  // waits for these loads leave the tile's loads in flight behind them).
+  // Buffer loads: a null xmax / wprep is an empty extent that reads 0 (no
+  // branch around a load), and image entries past the last take BUF_OOR
+  constexpr int WLO = NS * NTD * 64, NWL = ceil_div(WLO, 256), WHDR = NTD * 16 * 4;   // entries, per thread, header bytes
+  constexpr int XMR = 2;   // xmax slot quads per thread held in registers (the step's 2048 slots); more: a loop
+  f32x4 xmv[C::EARLY ? XMR : 1];
+  float xmr = 0.f;
+  s16x8 wph[C::EARLY ? NWL : 1], wpl[C::EARLY ? NWL : 1];
+  if constexpr (C::EARLY) {
+    const int xbytes = xm.p ? xm.n * 4 : 0;
+    const brsrc rxm = buf_rsrc(xm.p, xbytes);
+#pragma unroll
+    for (int k = 0; k < XMR; ++k) xmv[k] = buf_ld4(rxm, tid * 16 + k * 4096, 0);   // (the lane offset is what is range-checked)
+    const brsrc rw = buf_rsrc(wp, wp ? WHDR + 2 * WLO * 16 : 0);
+#pragma unroll
+    for (int nt = 0; nt < NTD; ++nt) ewn[nt] = __builtin_bit_cast(int, buf_ld1(rw, (lane & 15) * 4, nt * 64));
+#pragma unroll
+    for (int k = 0; k < NWL; ++k) {
+      const int idx = tid + k * 256;
+      const int vo = (WLO % 256 == 0 || idx < WLO) ? idx * 16 : BUF_OOR;
+      wph[k] = __builtin_bit_cast(s16x8, buf_ld4(rw, vo, WHDR));
+      wpl[k] = __builtin_bit_cast(s16x8, buf_ld4(rw, vo, WHDR + WLO * 16));
+    }
+    // slots past the registers' (never in the step): a dependent pass each
+    for (int o = XMR * 4096; o < xbytes; o += 4096) {
+      const f32x4 v = buf_ld4(rxm, tid * 16 + o, 0);
+      xmr = fmaxf(xmr, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+    }
+    PAIG_BSTAMP(0);
+  }
+
   auto xplane = [](int cq) { return cq * XPL + ((cq & 1) ? 16 : 0) + ((cq & 2) ? 64 : 0); };
-  // ---- zero what the staging never writes: the dY image's halo columns,
-  // its zero / spare slots, the X image's halo columns
-  for (int i = tid; i < FPT * ROWSD * 2 * PADL * CCD; i += 256) {
-    const int cc = i % CCD, hc = (i / CCD) % (2 * PADL), r = i / (CCD * 2 * PADL);
-    const int xc = hc < PADL ? hc : W + hc;
-    const int o = (r * RPD + xc * PSD + cc) * 8;
-    *reinterpret_cast<s16x8*>(Dh + o) = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    if (PM != 2) *reinterpret_cast<s16x8*>(Dl + o) = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-  }
-  if (tid < 2) {
-    *reinterpret_cast<s16x8*>(Dh + (C::ZSLOT + tid) * 8) = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    if (PM != 2) *reinterpret_cast<s16x8*>(Dl + (C::ZSLOT + tid) * 8) = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-  }
   // (UPS: again at every tile's staging -- the epilogue parks the tile's
   // full-resolution dX over the X image, halo columns included)
   auto zero_xhalo = [&]() {
@@ -308,17 +375,23 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
       if (PM != 2) *reinterpret_cast<s16x4*>(Xl + xplane(cq) + (r * TWX + xc) * 4) = s16x4{0, 0, 0, 0};
     }
   };
-  zero_xhalo();
-  PAIG_BSTAMP(13);
-
-  // ---- scales (PM 0): X per launch (ecx), dY per tile (ecd), the
-  // data-gradient weights per output channel (ewn)
-  int ecx = PAIG_A_EXP, ecd = PM == 0 && PAIG_SCALE_MODE < 2 ? 100 : 0;
-  float xsc = 1.f, dsc = __builtin_amdgcn_ldexpf(1.f, ecd);
-  float rmax = 0.f;   // range guard (fixed X scale without xmax slots)
-  int ewn[NTD];
-#pragma unroll
-  for (int nt = 0; nt < NTD; ++nt) ewn[nt] = 0;
+  // ---- zero what the staging never writes: the dY image's halo columns,
+  // its zero / spare slots, the X image's halo columns
+  auto zero_halos = [&]() {
+    for (int i = tid; i < FPT * ROWSD * 2 * PADL * CCD; i += 256) {
+      const int cc = i % CCD, hc = (i / CCD) % (2 * PADL), r = i / (CCD * 2 * PADL);
+      const int xc = hc < PADL ? hc : W + hc;
+      const int o = (r * RPD + xc * PSD + cc) * 8;
+      *reinterpret_cast<s16x8*>(Dh + o) = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (PM != 2) *reinterpret_cast<s16x8*>(Dl + o) = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    if (tid < 2) {
+      *reinterpret_cast<s16x8*>(Dh + (C::ZSLOT + tid) * 8) = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (PM != 2) *reinterpret_cast<s16x8*>(Dl + (C::ZSLOT + tid) * 8) = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    zero_xhalo();
+    PAIG_BSTAMP(13);
+  };
 
   // ---- data-gradient weights in fragment order ([s][nt][lane][8]): the
   // layer's transposed + flipped weights (dgrad image of paig_conv_wprep, or
@@ -334,16 +407,26 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
     return v;
   };
   __shared__ int sew[PM == 0 ? NTD * 16 : 1];
+  auto stage_w = [&]() {
   if (PM == 0 && wp != nullptr) {
-    const int* hdr = reinterpret_cast<const int*>(wp);
-    constexpr int HDR = NTD * 16 * 4 / 16;
+    if constexpr (C::EARLY) {
+      // the image entries loaded at kernel entry (the prologue's first wait)
 #pragma unroll
-    for (int nt = 0; nt < NTD; ++nt) ewn[nt] = hdr[nt * 16 + (lane & 15)];
-    const s16x8* img = wp + HDR;
-    constexpr int WLO = NS * NTD * 64;
-    for (int idx = tid; idx < NS * NTD * 64; idx += 256) {
-      *reinterpret_cast<s16x8*>(Wh + idx * 8) = img[idx];
-      *reinterpret_cast<s16x8*>(Wl + idx * 8) = img[WLO + idx];
+      for (int k = 0; k < NWL; ++k) {
+        const int idx = tid + k * 256;
+        if (WLO % 256 != 0 && idx >= WLO) break;
+        *reinterpret_cast<s16x8*>(Wh + idx * 8) = wph[k];
+        *reinterpret_cast<s16x8*>(Wl + idx * 8) = wpl[k];
+      }
+    } else {
+      const int* hdr = reinterpret_cast<const int*>(wp);
+#pragma unroll
+      for (int nt = 0; nt < NTD; ++nt) ewn[nt] = hdr[nt * 16 + (lane & 15)];
+      const s16x8* img = wp + WHDR / 16;
+      for (int idx = tid; idx < NS * NTD * 64; idx += 256) {
+        *reinterpret_cast<s16x8*>(Wh + idx * 8) = img[idx];
+        *reinterpret_cast<s16x8*>(Wl + idx * 8) = img[WLO + idx];
+      }
     }
   } else {
     if constexpr (PM == 0) {
@@ -381,8 +464,15 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
       if (PM != 2) *reinterpret_cast<s16x8*>(Wl + idx * 8) = vl;
     }
   }
-
   PAIG_BSTAMP(14);
+  };
+  // today's order where the early loads are off: halos, weights, addressing,
+  // the first tile's prefetch, xmax
+  if constexpr (!C::EARLY) {
+    zero_halos();
+    stage_w();
+  }
+
   // ---- data-gradient fragment offsets (slots): pixel base per M-tile,
   // (tap, chunk) per k-step
   int pbase[MW];
@@ -878,7 +968,22 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
   PAIG_BSTAMP(15);
   issue(tile_of(lt));
   PAIG_BSTAMP(16);
-  if (PM == 0 && xm.p) {
+  if constexpr (C::EARLY) {
+    // behind the prefetch's issue: LDS stores that no load is waited for,
+    // then the weight fragments and the xmax partial (their loads are the
+    // oldest in flight, and returned in the same round trip as the tile's
+    // first dY loads).  No barrier here: the halos, the fragments and sxm
+    // are first read after the first tile's loop-top barrier (sxm) and its
+    // commit barrier (the images), and none of them is written again (UPS:
+    // the X halos are, by every commit, before that barrier)
+    zero_halos();
+    stage_w();
+    float m = xmr;
+#pragma unroll
+    for (int k = 0; k < XMR; ++k) m = fmaxf(m, fmaxf(fmaxf(xmv[k][0], xmv[k][1]), fmaxf(xmv[k][2], xmv[k][3])));
+    m = wave_max_u(m);
+    if (lane == 0) sxm[wv] = m;
+  } else if (PM == 0 && xm.p) {
     // the launch's X exponent: max over the forward's per-block slots
     float m = 0.f;
     for (int i = tid * 4; i < xm.n; i += 1024) {
@@ -887,10 +992,10 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
     }
     m = wave_max_u(m);
     if (lane == 0) smax[wv] = m;
-    __syncthreads();
+    __syncthreads();   // the four partials are written
     m = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
     if (m > 0.f) ecx = f16_scale_exp(m);   // all-zero slots (never written): the fixed scale, guarded
-    __syncthreads();
+    __syncthreads();   // ... and read, before the first tile_max() reuses smax
   }
   PAIG_BSTAMP(17);
   if constexpr (PM == 0) xsc = __builtin_amdgcn_ldexpf(1.f, ecx);
@@ -902,10 +1007,21 @@ conv_bwd_split_k(FView x, FView dy, FViewW dx, FView aux, const float* __restric
     const int f0 = (tile / NRB) * FPT, y0 = (tile % NRB) * RT;
     if constexpr (PF) fold(tile);
     if constexpr (PM == 0 && PAIG_SCALE_MODE < 2) tile_max();
-    __syncthreads();   // the previous tile's fragment reads are done
+    // the previous tile's fragment reads are done (WAR on both images) and
+    // smax holds every wave's tile maximum; on the block's first tile also:
+    // sxm holds every wave's xmax partial
+    __syncthreads();
+    if constexpr (C::EARLY) {
+      if (lt == (int)blockIdx.x) {
+        // the launch's X exponent: max over the forward's per-block slots
+        const float m = fmaxf(fmaxf(sxm[0], sxm[1]), fmaxf(sxm[2], sxm[3]));
+        if (m > 0.f) ecx = f16_scale_exp(m);   // all-zero slots (never written) or no xmax: the fixed scale, guarded
+        xsc = __builtin_amdgcn_ldexpf(1.f, ecx);
+      }
+    }
     PAIG_BSTAMP(1);
     commit(tile);
-    __syncthreads();
+    __syncthreads();   // the tile's images are staged (RAW for the fragment reads)
     PAIG_BSTAMP(2);
     // this tile's ReLU' mask for the epilogue (AUXP), issued before the next
     // tile's prefetch: the epilogue then waits for it alone

@@ -30,7 +30,9 @@ LAYERS = {
 }
 PHASES = ["setup", "wait+max+bar", "commit-tail", "issue", "wgrad", "dgrad", "epilogue", "slab", "put_d", "ups_win",
           "ups_bar", "ups_x"]
-# the once-per-block phases split further (stamp slots 13..19; slot 0 / 7 keep the rest of setup / the bias reduction)
+# the once-per-block phases split further (stamp slots 13..19; slot 0 / 7 keep the rest of setup / the bias reduction).
+# Split kernels with the entry loads (conv_bwd.hip sbwd_early) walk them as rest (the entry loads' issue), addr,
+# issue0 (with the wait for the first dY and the entry loads), halo0, wcopy (LDS stores only), xmax (register + wave max)
 SETUP = {13: "halo0", 14: "wcopy", 15: "addr", 16: "issue0", 17: "xmax", 0: "rest"}
 SLAB = {18: "put_w", 19: "tail", 7: "bias"}
 NST = 20
