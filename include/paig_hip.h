@@ -31,7 +31,7 @@ extern "C" {
 /* Version of this interface: bumped whenever an entry point's argument list
  * or a data layout it exchanges changes (the Python binding refuses a library
  * of another version). */
-#define PAIG_ABI_VERSION 12
+#define PAIG_ABI_VERSION 13
 const char* paig_last_error(void);
 int paig_abi_version(void);
 /* f16 range guard of the split-precision path.  Activations and gradients
@@ -506,7 +506,10 @@ int paig_localiser_bwd(const float* dpos, const float* x1, const float* h1, cons
  * MLP's [W0|b0|W2|b2|W4|b4] gradient to dmlp (overwritten) and the physics
  * parameters' to gparam0/1 (fp64; workspace paig_velmlp_rollout_bwd_workspace
  * bytes).  alt_vel (the linear velocity encoder) is not covered.  cell: any
- * kind of paig_rollout_fwd (D = 2K), the 2-D kinds 3 and 4 included. */
+ * kind of paig_rollout_fwd (D = 2K), the 2-D kinds 3 and 4 included.  The
+ * black-box LSTM cell (paig_rollout_lstm_fwd / _bwd) is no kind of
+ * paig_rollout_fwd and is not taken here: any other cell value is
+ * PAIG_E_UNSUPPORTED. */
 int paig_velmlp_rollout_fwd(int cell, const float* pos, int B, int Te, int K, int S, const float* W0, const float* b0,
                             const float* W2, const float* b2, const float* W4, const float* b4, float* X, float* h1,
                             float* h2, float* vel0, const float* dt, const double* p0, const double* p1, float* pvs,
@@ -537,6 +540,38 @@ int paig_rollout_bwd(int cell, const float* pvs, const float* dpos_roll, const f
                      const double* p0, const double* p1, float* dpos0, float* dvel0, double* part, double* gparam0,
                      double* gparam1, int accumulate, int B, int D, int R, void* stream);
 
+/* ---- black-box rollout cell: an LSTM with a linear read-out in the place of
+ *      the physics equations, all R steps in one launch.  Replaces stepping
+ *      nn.LSTMCell(2D, H) + nn.Linear(H, 2D) R times from Python (the
+ *      reference lists "lstm" in CELLS, physics_models.py:35, but its rollout
+ *      loop :231-239 cannot call it; gate order i, f, g, o as aten lstm_cell):
+ *        x_t = [(pos_t - half) / half, vel_t / half]        h_0 = c_0 = 0
+ *        z   = W_ih x_t + b_ih + W_hh h_t + b_hh
+ *        c'  = sig(z_f) c + sig(z_i) tanh(z_g);  h' = sig(z_o) tanh(c')
+ *        y   = W_p h' + b_p;  pos' = pos + half y[:D];  vel' = vel + half y[D:]
+ *      w_ih [4H][2D], w_hh [4H][H], b_ih, b_hh [4H], w_p [2D][H], b_p [2D];
+ *      pos0 / vel0 / pvs / dpos_roll / dpvs / dpos0 / dvel0 as paig_rollout_fwd
+ *      / _bwd (vel0 and dvel0 nullable).  D in {4, 6}, H a multiple of 4 in
+ *      [4, 128]: anything else is PAIG_E_UNSUPPORTED.  Exact f32 products.
+ *      ws (paig_rollout_lstm_workspace bytes, 16-byte aligned): the forward
+ *      saves there what the backward reads (post-activation gates [B][R][4H],
+ *      c and h per step, x_t); a null ws saves nothing (inference) and gives
+ *      the same pvs bit for bit.  The backward (same ws, after that forward)
+ *      walks t = R .. 1 in one launch, leaves dz [B][R][4H] and dy [B][R][2D]
+ *      in ws and forms the six parameter gradients from them with paig_gemm
+ *      (dW = dz^T x, dz^T h_t, dy^T h_t+1) and paig_colsum: no atomics, two
+ *      runs are bit-identical.  accumulate != 0 adds to the parameter
+ *      gradients (as paig_rollout_bwd); dpos0 / dvel0 are overwritten. */
+size_t paig_rollout_lstm_workspace(int B, int D, int H, int R);
+int paig_rollout_lstm_fwd(const float* pos0, long long pos0_ld, const float* vel0, const float* w_ih,
+                          const float* w_hh, const float* b_ih, const float* b_hh, const float* w_p, const float* b_p,
+                          float half, float* pvs, void* ws, size_t ws_bytes, int B, int D, int H, int R,
+                          void* stream);
+int paig_rollout_lstm_bwd(const float* dpos_roll, const float* dpvs, const float* w_ih, const float* w_hh,
+                          const float* w_p, float half, float* dpos0, float* dvel0, float* dw_ih, float* dw_hh,
+                          float* db_ih, float* db_hh, float* dw_p, float* db_p, int accumulate, void* ws,
+                          size_t ws_bytes, int B, int D, int H, int R, void* stream);
+
 /* ---- spatial-transformer decoder + compositing + per-frame SSE
  *      (conv_st_decoder physics_models.py:151-199, stn stn.py:5-16,
  *       compute_loss physics_models.py:119-135), all frames in one launch */
@@ -556,7 +591,9 @@ int paig_decoder_fwd(const float* pos, long long pos_outer, long long pos_inner,
  * launch: they are independent, and the rollout's one-thread-per-sequence
  * recurrence no longer holds the GPU alone.  The one-CU decoder shapes only:
  * (K, H) in {(2, 32), (3, 36), (2, 64)}, 16-byte aligned frames; the cell / D
- * pairs of paig_rollout_fwd */
+ * pairs of paig_rollout_fwd.  The black-box LSTM cell (paig_rollout_lstm_fwd)
+ * is not among them (no merged launch for it): any other cell value is
+ * PAIG_E_UNSUPPORTED. */
 int paig_decoder_fwd_rollout(int cell, const float* pos0, long long pos0_ld, const float* vel0, const float* dt,
                              const double* p0, const double* p1, float* pvs, int B, int D, int R, const float* pos,
                              long long pos_outer, long long pos_inner, int pos_grp, const float* tmpl,

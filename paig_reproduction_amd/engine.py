@@ -92,6 +92,9 @@ def live_steps(d_out, d_sse_roll, ent_roll):
     return 0
 
 
+LSTM_CELL = 5   # Layout.cell of lstm_ode_cell (cells.lstm_ode_cell.KIND)
+
+
 class Layout:
     """Static shapes of one step (from the PhysicsNet config and batch)."""
 
@@ -116,9 +119,11 @@ class Layout:
         else:
             self.F = frames
         self.alt_vel = model.alt_vel
-        # paig_rollout_fwd's cell kinds (3, 4: the opt-in split-size-2 cells)
+        # paig_rollout_fwd's cell kinds (3, 4: the opt-in split-size-2 cells);
+        # 5: the black-box LSTM cell, on paig_rollout_lstm_fwd / _bwd
         self.cell = {"spring_ode_cell": 0, "bouncing_ode_cell": 1, "gravity_ode_cell": 2, "spring2d_ode_cell": 3,
-                     "bouncing2d_ode_cell": 4}[model.cell_type]
+                     "bouncing2d_ode_cell": 4, "lstm_ode_cell": LSTM_CELL}[model.cell_type]
+        self.lstm_H = model.rollout_cell.recurrent_units if self.cell == LSTM_CELL else 0
         self.unet = self.H >= 40 if net is None else net == "unet"
         L = lib()
         self.net = 1 if self.unet else 0   # paig_unet_*: 0 ShallowUNet(hidden 8), 1 UNet(hidden 16)
@@ -277,6 +282,7 @@ class StepState:
     v2: object = None           # forward: velocity MLP hidden 2; backward
     vel0: object = None         # forward: initial velocities, None when input_steps == 1; backward
     pvs: object = None          # forward: rollout positions and velocities; backward
+    lstm_ws: object = None      # forward (lstm_ode_cell, a backward may follow): the cell's saved gates / states; backward
     wprep: dict = None          # _unet_forward: split weight images {(conv, kind): pointer}; _encoder_forward
     wprep_buf: object = None    # _unet_forward: the buffer behind wprep (kept alive)
     logits: object = None       # _unet_forward (head not fused): the U-Net's logits; mask softmax, _unet_backward
@@ -455,9 +461,15 @@ class Engine:
         """(cell, pos0, ld, vel0, dt, p0, p1, pvs, B, D, R): the rollout starts
         at the last input step's encoded positions."""
         lay = S.lay
+        pos0 = (ptr(S.enc_pos) + (lay.ins - 1) * lay.D * 4, lay.Te * lay.D, ptr(S.vel0))
+        if lay.cell == LSTM_CELL:
+            # paig_rollout_lstm_fwd's: (pos0, ld, vel0, W_ih, W_hh, b_ih, b_hh,
+            # W_p, b_p, s, pvs, workspace, bytes, B, D, H, R)
+            ws = S.lstm_ws
+            return (*pos0, *[ptr(p) for p in self.cell_params(lay)], float(lay.H / 2), ptr(S.pvs), ptr(ws),
+                    ws.numel() * 4 if ws is not None else 0, lay.B, lay.D, lay.lstm_H, lay.R)
         dt, p0, p1 = self.cell_params(lay)
-        return (lay.cell, ptr(S.enc_pos) + (lay.ins - 1) * lay.D * 4, lay.Te * lay.D, ptr(S.vel0), ptr(dt), ptr(p0),
-                ptr(p1), ptr(S.pvs), lay.B, lay.D, lay.R)
+        return (lay.cell, *pos0, ptr(dt), ptr(p0), ptr(p1), ptr(S.pvs), lay.B, lay.D, lay.R)
 
     def _decoder_ops(self, S):
         """The decoder calls of this forward's sigma and VFN sources."""
@@ -546,6 +558,8 @@ class Engine:
                 S.v1 = _empty(K * B * 100, dev)
                 S.v2 = _empty(K * B * 100, dev)
         S.pvs = _empty(B * (lay.R + 1) * 2 * D, dev)
+        if lay.cell == LSTM_CELL and need_saved:   # what BPTT reads; inference saves nothing
+            S.lstm_ws = _empty(L.paig_rollout_lstm_workspace(B, D, lay.lstm_H, lay.R) // 4, dev)
         roll = self._rollout_args(S)
         vel_act = (ptr(S.Xv), ptr(S.v1), ptr(S.v2), ptr(S.vel0))
         dec = self._decoder_ops(S)
@@ -561,7 +575,10 @@ class Engine:
             self.linear(S.Xv, K * B, "velocity_encoder.init_vel_linear", S.vel0, 0, st, ws)
         elif S.vel0 is not None:   # the whole MLP (packing fused) in one launch
             L.paig_velmlp_fwd(ptr(enc_pos), B, lay.Te, K, lay.ins, *self._velmlp_params(), *vel_act, st)
-        if not merge_roll:   # the physics rollout (all R steps in one launch)
+        if lay.cell == LSTM_CELL:   # the black-box cell: all R LSTM steps in one launch (never merged)
+            with self._p("rollout_lstm_fwd"):
+                L.paig_rollout_lstm_fwd(*roll, st)
+        elif not merge_roll:   # the physics rollout (all R steps in one launch)
             L.paig_rollout_fwd(*roll, st)
         if not fuse_vfn:
             L.paig_vfn_fwd_multi(*self._vfn_fwd_args(S), st)
@@ -775,6 +792,8 @@ class Engine:
 
     def cell_params(self, lay):
         m = self.model
+        if lay.cell == LSTM_CELL:   # (W_ih, W_hh, b_ih, b_hh, W_p, b_p): fp32, no dt
+            return m.rollout_cell.weights()
         dt = m.rollout_cell.dt
         if lay.cell in (0, 3):
             return dt, m.rollout_cell.k, m.rollout_cell.equil
@@ -849,12 +868,22 @@ class Engine:
         # ---- rollout adjoint -> d pos0, d vel0, physics params; velocity encoder backward
         prm = self.cell_params(lay)
         gk = gq = None
-        if lay.cell in (0, 3):
+        if lay.cell == LSTM_CELL:
+            if S.lstm_ws is None:
+                raise PaigError("lstm_ode_cell: the forward saved no workspace for its backward")
+            names = ["rollout_cell." + n for n in ("lstm.weight_ih", "lstm.weight_hh", "lstm.bias_ih", "lstm.bias_hh",
+                                                   "proj.weight", "proj.bias")]
+            with self._p("rollout_lstm_bwd"):
+                L.paig_rollout_lstm_bwd(ptr(dpos_roll), ptr(d_pvs), ptr(prm[0]), ptr(prm[1]), ptr(prm[4]),
+                                        float(lay.H / 2), ptr(dpos0), ptr(dvel0), *[ptr(self.g(n)) for n in names], 0,
+                                        ptr(S.lstm_ws), S.lstm_ws.numel() * 4, B, D, lay.lstm_H, R, st)
+        elif lay.cell in (0, 3):
             gk, gq = self.g("rollout_cell.k"), self.g("rollout_cell.equil")
         elif lay.cell == 2:
             gk = self.g("rollout_cell.g")
-        L.paig_rollout_bwd(lay.cell, ptr(S.pvs), ptr(dpos_roll), ptr(d_pvs), ptr(prm[0]), ptr(prm[1]), ptr(prm[2]),
-                           ptr(dpos0), ptr(dvel0), ptr(rpart), ptr(gk), ptr(gq), 0, B, D, R, st)
+        if lay.cell != LSTM_CELL:
+            L.paig_rollout_bwd(lay.cell, ptr(S.pvs), ptr(dpos_roll), ptr(d_pvs), ptr(prm[0]), ptr(prm[1]), ptr(prm[2]),
+                               ptr(dpos0), ptr(dvel0), ptr(rpart), ptr(gk), ptr(gq), 0, B, D, R, st)
         if S.vel0 is not None and lay.alt_vel:
             self.linear_bwd(S.Xv, dvel0, K * B, "velocity_encoder.init_vel_linear", dXv, None, 0, st, S.ws)
         elif S.vel0 is not None:   # one launch; its partial weight grads join the U-Net's batched slab reduction

@@ -10,7 +10,11 @@ the split-size-1 quirk Q3.  Gravity recomputes A = exp(g) exp(2m) per step
 (the reference computes it once in __init__, Q4).
 
 spring2d_ode_cell / bouncing2d_ode_cell (rollout kinds 3 / 4) are the opt-in
-fix of Q3: the same cells with split size 2, two objects in the plane."""
+fix of Q3: the same cells with split size 2, two objects in the plane.
+
+lstm_ode_cell is the black-box baseline (not in the reference, whose "lstm"
+table entry its rollout cannot call): a learned LSTM step in the place of the
+equations, on paig_rollout_lstm_fwd/bwd (csrc/rollout_lstm.hip)."""
 import numpy as np
 import torch
 import torch.nn as tnn
@@ -88,3 +92,43 @@ class gravity_ode_cell(ode_cell):
     @property
     def A(self):
         return torch.exp(self.g.detach()) * torch.exp(2 * self.m.detach())
+
+
+class lstm_ode_cell(tnn.Module):
+    """The black-box rollout cell: no equation, no dt.  One step is
+
+        x = [(pos - s) / s, vel / s]              s = frame side / 2
+        h, c = LSTMCell(x, (h, c))                h = c = 0 at the start of every rollout
+        y = proj(h);  pos += s y[:D];  vel += s y[D:]
+
+    with lstm = nn.LSTMCell(2D, H) and proj = nn.Linear(H, 2D), D =
+    input_size.  Torch's default initialisation; proj is scaled by 0.1, so a
+    fresh cell moves objects by about a pixel per step."""
+    KIND = 5   # no kind of paig_rollout_fwd: paig_rollout_lstm_fwd / _bwd
+    H_MAX = 128
+
+    def __init__(self, input_size, hidden_size, recurrent_units=100, half=16.0):
+        super().__init__()
+        H = recurrent_units
+        if isinstance(H, bool) or not isinstance(H, int) or H % 4 != 0 or not 4 <= H <= self.H_MAX:
+            raise ValueError(f"lstm_ode_cell: recurrent_units={H!r} must be a multiple of 4 in [4, {self.H_MAX}]")
+        self.input_size = input_size
+        self.hidden_size = hidden_size
+        self.recurrent_units = H
+        self.half = float(half)
+        self.lstm = tnn.LSTMCell(2 * input_size, H)
+        self.proj = tnn.Linear(H, 2 * input_size)
+        with torch.no_grad():
+            self.proj.weight.mul_(0.1)
+            self.proj.bias.mul_(0.1)
+
+    def weights(self):
+        """(W_ih, W_hh, b_ih, b_hh, W_p, b_p), the kernels' argument order."""
+        return (self.lstm.weight_ih, self.lstm.weight_hh, self.lstm.bias_ih, self.lstm.bias_hh, self.proj.weight,
+                self.proj.bias)
+
+    def forward(self, poss, vels):
+        """One step from a zero hidden state (paig_rollout_lstm_fwd/bwd with
+        R = 1): poss, vels [B, D] -> (poss, vels)."""
+        from paig_reproduction_amd.nn.network import native_modules as _nm
+        return _nm.cell_forward(self, poss, vels)

@@ -25,6 +25,9 @@ Additive flags only:
         (the cells with split size 2: a vector spring between (x0, y0) and (x1, y1); four walls)
         instead of the reference's split-size-1 cells (quirk Q3).  Off by default; the
         state_dict is the same, so checkpoints move between the two.  An error for 3bp_color.
+  --blackbox_dynamics            the black-box baseline: every task rolls out with lstm_ode_cell
+        (nn.LSTMCell of --recurrent_units hidden units + a linear read-out, on the device) instead
+        of its physics cell.  Off by default; an error together with --physics_2d.
   --synthetic_device {0,1}       1: with --synthetic N and the task's npz missing,
         render the data on the GPU instead (nn/datasets/synth_device.py: HIP
         integrators + rasteriser) and keep it in HBM; no npz is written.  Same
@@ -137,6 +140,10 @@ def build_parser():
     p.add_argument("--physics_2d", action="store_true",
                    help="two objects in the plane: the task's spring / bouncing cell with split size 2 (a vector "
                         "spring, four walls) instead of the reference's split-size-1 cell; not for 3bp_color")
+    p.add_argument("--blackbox_dynamics", action="store_true",
+                   help="the black-box baseline: every task rolls out with lstm_ode_cell (an LSTM of "
+                        "--recurrent_units hidden units and a linear read-out) instead of its physics cell; "
+                        "not with --physics_2d")
     return p
 
 
@@ -146,7 +153,12 @@ CELLS_2D = {"spring_ode_cell": "spring2d_ode_cell", "bouncing_ode_cell": "bounci
 
 def task_cell(args):
     """The rollout cell of args.task: TASKS' preset, or under --physics_2d its
-    2-D class (an error for a task whose cell has none)."""
+    2-D class (an error for a task whose cell has none), or under
+    --blackbox_dynamics the learned lstm_ode_cell for every task."""
+    if getattr(args, "blackbox_dynamics", False):
+        if args.physics_2d:
+            raise SystemExit("--blackbox_dynamics replaces the physics cell: it cannot be combined with --physics_2d")
+        return "lstm_ode_cell"
     cell = TASKS[args.task][2]
     if not args.physics_2d:
         return cell
@@ -206,6 +218,9 @@ def main(argv=None):
     data_file, test_data_file, cell_type, seq_len, test_seq_len, input_steps, pred_steps, input_size = \
         TASKS[args.task]
     cell_type = task_cell(args)   # the training model and the test-time model alike
+    if args.blackbox_dynamics and args.physics_lr_mult != 1.0:
+        logger.warning("--physics_lr_mult %g has no effect with --blackbox_dynamics: lstm_ode_cell has no fp64 "
+                       "physics parameter, its weights step with --base_lr", args.physics_lr_mult)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
