@@ -114,6 +114,29 @@ constexpr int sfwd_pick(int CIN, int COUT, int H, int W, int KS, bool UPS, int P
   return 0;
 }
 
+// The staging loads go through buffer descriptors of one tile's frames
+// (split_common.h), and each staging unit's addressing -- its byte offset in
+// the tile's frames less the row origin, its row less the halo -- is formed
+// once per block and held across the tile loop (form 2).  The register
+// escape, per instantiation (-Rpass-analysis=kernel-resource-usage against
+// the address-select form): form 1 recomputes the addressing per tile (the
+// bf16 kernels: held across the loop it costs 4-30 registers and a wave per
+// SIMD on ten of them); form 0 keeps the address-select staging and the
+// serial prologue, for the kernels that lose a wave per SIMD or gain scratch
+// in both descriptor forms (cause not found; none is in the spring step)
+constexpr int sfwd_form(int CIN, int COUT, int H, int PM, bool POOL) {
+  if (CIN == 16 && COUT == 48 && H == 64) return 0;                   // mnist 16 <-> 48 at 64^2: 3 -> 2 waves (f16 and bf16)
+  if (CIN == 64 && COUT == 96 && H == 16 && POOL) return 0;           // 12 more bytes of scratch
+  if (PM == 2 && CIN == 3 && COUT == 16 && H == 64 && POOL) return 0; // 5 -> 4 waves
+  if (PM == 2 && COUT == 32 && H == 32 && (CIN == 16 || CIN == 32) && !POOL) return 0;   // 4 -> 3, 3 -> 2 waves
+  return PM == 2 ? 1 : 2;
+}
+// 256-entry rounds of the pre-split weight image (hi + lo: 8 registers each)
+// a thread loads at kernel entry; the rest of a larger slice is copied after
+// them, round by round (the UNet's layers of >= 64 input channels and 3bp /
+// mnist slices of 3-4 output tiles at 32 channels)
+constexpr int SFWD_WEARLY = 6;
+
 template <int CIN, int COUT, int H, int W, int KS, bool UPS, int PM>
 struct SFwdCfg {
   static constexpr int KK = KS * KS, PADL = KS / 2;
@@ -256,6 +279,38 @@ __device__ __forceinline__ void conv_fwd_split_body(FView in, FViewW out, FView 
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) ewn[nt] = 0;
   __shared__ int sew[PM == 0 ? NT * 16 : 1];   // in-kernel staging: the slice's channel exponents
+  // ---- everything the block reads once is issued here, oldest first: the
+  // bias, and (PM 0) paig_conv_wprep's channel exponents and the first WNE
+  // rounds of this slice's hi / lo images, into registers.  The first tile's
+  // prefetch follows, and the halo zeroing and the images' LDS stores run
+  // under its latency: one memory round trip where there were three (vmcnt
+  // retires in order, so the waits for these loads leave the tile's loads in
+  // flight behind them).  Buffer loads: a null bias / image is an empty
+  // extent that reads 0 (no branch around a load; the in-kernel staging then
+  // forms ewn itself), entries past the slice take BUF_OOR
+  constexpr int NTT = NT * C::NB, WLO = NS * NTT * 64, WSL = NS * NT * 64, WHDR = NTT * 16 * 4;   // entries: whole image, slice; header bytes
+  constexpr int FORM = sfwd_form(CIN, COUT, H, PM, POOL);   // 0: address selects, serial prologue (the escape)
+  constexpr bool HOIST = FORM == 2;
+  constexpr int WNE = PM == 0 && FORM > 0 ? (ceil_div(WSL, 256) < SFWD_WEARLY ? ceil_div(WSL, 256) : SFWD_WEARLY) : 0;
+  float bvs[NT];   // the bias of this lane's output channels (block constant)
+  s16x8 wph[WNE > 0 ? WNE : 1], wpl[WNE > 0 ? WNE : 1];
+  if constexpr (FORM > 0) {
+    const brsrc rb = buf_rsrc(bias, bias ? COUT * 4 : 0);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) bvs[nt] = buf_ld1(rb, (co0 + nt * 16 + (lane & 15)) * 4, 0);   // (channels past COUT: past the extent)
+    if constexpr (WNE > 0) {
+      const brsrc rw = buf_rsrc(wp, wp ? WHDR + 2 * WLO * 16 : 0);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) ewn[nt] = __builtin_bit_cast(int, buf_ld1(rw, (co0 + (lane & 15)) * 4, nt * 64));
+#pragma unroll
+      for (int k = 0; k < WNE; ++k) {
+        const int idx = tid + k * 256, s = idx / (NT * 64), r = idx - s * (NT * 64);
+        const int vo = (WSL % 256 == 0 || idx < WSL) ? ((s * NTT + (int)blockIdx.y * NT) * 64 + r) * 16 : BUF_OOR;
+        wph[k] = __builtin_bit_cast(s16x8, buf_ld4(rw, vo, WHDR));
+        wpl[k] = __builtin_bit_cast(s16x8, buf_ld4(rw, vo, WHDR + WLO * 16));
+      }
+    }
+  }
   // ---- zero the halo columns (never written by the staging; again after
   // UPT's epilogue, which keeps its dX tile in the images' LDS)
   auto zero_halo = [&]() {
@@ -269,7 +324,7 @@ __device__ __forceinline__ void conv_fwd_split_body(FView in, FViewW out, FView 
       }
     }
   };
-  zero_halo();
+  if constexpr (FORM == 0) zero_halo();
   // ---- per-lane fragment slot offsets: pixel base per M-tile, (tap, chunk) per k-step
   int pbase[MW];
 #pragma unroll
@@ -373,14 +428,62 @@ __device__ __forceinline__ void conv_fwd_split_body(FView in, FViewW out, FView 
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) tinv[nt] = __builtin_amdgcn_ldexpf(1.f, -(e + ewn[nt]));
   };
-  auto issue = [&](int t) {
-    const int f0 = (t / NRB) * FPT, y0 = (t % NRB) * RT;
-    if constexpr (UPS) {
-      up.issue(in, F, f0, y0, tid);
+  // ---- addressing that depends on the thread alone, once per block (HOIST).
+  // Per staging unit: its byte offset inside the tile's frames less the
+  // tile's row origin (vo) and its image row less the halo (row: frame row
+  // y0 + row; idle lanes get a row that no tile has).  Whole-frame tiles
+  // (NRB == 1: y0 = 0) know their halo rows here: those units' offsets are
+  // BUF_OOR from the start.  Per tile there remain scalar work (the
+  // descriptor of the tile's frames: frame tails and the prefetch after the
+  // last tile lie past its extent) and, on row tiles, one add and one select
+  // per unit.  Frames of one tile are fs apart (FPT > 1 only for plain views)
+  auto row_ok = [&](int gy) { return (unsigned)gy < (unsigned)H; };
+  auto s_unit = [&](int i, int& vo, int& row) {
+    const int xp = UPX * (i % W2), r = (i / W2) % ROWS, cc = (i / (W2 * ROWS)) % CC, fi = i / (W2 * ROWS * CC);
+    row = i < NI ? r - PADL : -(1 << 20);
+    vo = ((FPT > 1 ? fi * (int)in.fs : 0) + cc * 8 * (int)PLANE + (r - PADL) * W + xp) * 4;
+    if (NRB == 1 && !row_ok(row)) vo = BUF_OOR;
+  };
+  constexpr int NLH = HOIST && !UPS ? NL : 1;
+  int svo[NLH], srow[NLH];
+  if constexpr (HOIST && !UPS) {
+#pragma unroll
+    for (int l = 0; l < NL; ++l) s_unit(tid + l * 256, svo[l], srow[l]);
+  }
+  // unit l of this thread (not hoisted: from a thread id the compiler cannot
+  // hoist the arithmetic of)
+  auto s_get = [&](int l, int& vo, int& row) {
+    if constexpr (HOIST) {
+      vo = svo[l];
+      row = srow[l];
     } else {
-      // branch-free: every lane loads (out-of-tile lanes re-read the tile's
-      // first pixels) and zeroes afterwards; 32-bit offsets from the tile's
-      // frame (frames of one tile are fs apart: FPT > 1 only for plain views)
+      s_unit(opaque(tid) + l * 256, vo, row);
+    }
+  };
+  // PF: pooled gradient / window code offsets less the window row (two more
+  // registers per unit, which the pool-fold kernels do not have: per tile)
+  auto pf_unit = [&](int i, int& po, int& co) {
+    constexpr int HP = H / 2, WP = W / 2;
+    const int xp = UPX * (i % W2), cc = (i / (W2 * ROWS)) % CC, fi = i / (W2 * ROWS * CC);
+    po = ((FPT > 1 ? fi * (int)pout.fs : 0) + cc * 8 * (HP * WP) + (xp >> 1)) * 4;
+    co = (FPT > 1 ? fi * (int)pout.code_fs : 0) + (cc * (HP * WP) + (xp >> 1)) * 8;
+  };
+  constexpr int NUH = HOIST && UPS ? UP::NLS : 1;
+  int uvo[NUH], urow[NUH];
+  if constexpr (HOIST && UPS) {
+#pragma unroll
+    for (int l = 0; l < UP::NLS; ++l) UP::unit(tid + l * 256, (int)in.fs, uvo[l], urow[l]);
+  }
+  // frames of the tile at f0 that the views own (0 past the last tile)
+  auto tile_nf = [&](int f0) {
+    const int n = F - f0;
+    return n < FPT ? n : FPT;
+  };
+  static_assert(FORM > 0 || (!UPS && !UPT && !PF), "the address-select form covers the plain forward / dgrad only");
+  auto issue = [&](int t) {
+    const int f0 = (t / NRB) * FPT, y0 = (t % NRB) * RT, nf = tile_nf(f0);
+    if constexpr (FORM == 0) {
+      // one 64-bit address per unit: out-of-tile lanes read zero planes
       const float* fb = in.frame(f0);
 #pragma unroll
       for (int l = 0; l < NL; ++l) {
@@ -390,22 +493,64 @@ __device__ __forceinline__ void conv_fwd_split_body(FView in, FViewW out, FView 
         const bool ok = i < NI && f0 + fi < F && gy >= 0 && gy < H;
         const int off = fi * (int)in.fs + cc * 8 * (int)PLANE + gy * W + xp;
         static_assert(8 * PLANE <= 8 * 4096, "paig_zero_planes covers the unit");
-        const float* base = ok ? fb + off : paig_zero_planes;   // one address per unit
+        const float* base = ok ? fb + off : paig_zero_planes;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
           // channels past CIN (CIN % 8 != 0 only) read a zero of their own
           const float* q = CIN % 8 == 0 || cc * 8 + c < CIN ? base + c * (int)PLANE : paig_zeros;
           pre[l][c] = UPX == 2 ? *reinterpret_cast<const float2*>(q) : make_float2(*q, 0.f);
         }
+      }
+      return;
+    }
+    const brsrc rin = tile_rsrc(in.frame(f0), in.fs, nf, CIN * (int)PLANE);
+    if constexpr (UPS) {
+      if constexpr (HOIST) {
+        up.issue(rin, y0, uvo, urow);
+      } else {
+        int uo[UP::NLS], ur[UP::NLS];
+#pragma unroll
+        for (int l = 0; l < UP::NLS; ++l) UP::unit(opaque(tid) + l * 256, (int)in.fs, uo[l], ur[l]);
+        up.issue(rin, y0, uo, ur);
+      }
+    } else {
+      // branch-free: every lane loads; idle lanes, halo rows outside the
+      // frame (they would land in the neighbouring frame or plane, inside the
+      // descriptor) and channels past CIN take BUF_OOR and read 0
+      brsrc rp, rc;
+      if constexpr (PF) {
+        rp = tile_rsrc(pout.frame(f0), pout.fs, nf, CIN * (H / 2) * (W / 2));
+        rc = tile_rsrc(pout.code + (long long)f0 * pout.code_fs, pout.code_fs, nf, CC * (H / 2) * (W / 2) * 8, 1);
+      }
+#pragma unroll
+      for (int l = 0; l < NL; ++l) {
+        int vo0, row;
+        s_get(l, vo0, row);
+        const int vo = NRB == 1 ? vo0 : (row_ok(y0 + row) ? vo0 + y0 * W * 4 : BUF_OOR);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          int voc = vo;
+          if constexpr (CIN % 8 != 0) {
+            if (CC == 1 && c >= CIN) {   // no such channel in any unit
+              pre[l][c] = make_float2(0.f, 0.f);
+              continue;
+            }
+            if (c >= CIN % 8 && ((tid + l * 256) / (W2 * ROWS)) % CC == CC - 1) voc = BUF_OOR;
+          }
+          pre[l][c] = UPX == 2 ? buf_ld2(rin, voc, c * (int)PLANE * 4) : make_float2(buf_ld1(rin, voc, c * (int)PLANE * 4), 0.f);
+        }
         if constexpr (PF) {
           constexpr int HP = H / 2, WP = W / 2;
-          const int pw = (gy >> 1) * WP + (xp >> 1);
-          const float* pb = ok ? pout.frame(f0) + fi * (int)pout.fs + cc * 8 * (HP * WP) + pw : paig_zero_planes;
+          const int gy = y0 + row;
+          const bool ok = NRB == 1 ? vo != BUF_OOR : row_ok(gy);
+          int po, co;
+          pf_unit(opaque(tid) + l * 256, po, co);
+          const int wr = (gy >> 1) * WP;   // the window's row
+          const int vp = ok ? po + wr * 4 : BUF_OOR;
 #pragma unroll
-          for (int c = 0; c < 8; ++c) dpv[l][c] = pb[c * (HP * WP)];
-          const unsigned char* cb = ok ? pout.code + (long long)(f0 + fi) * pout.code_fs + ((long long)cc * HP * WP + pw) * 8
-                                       : reinterpret_cast<const unsigned char*>(paig_zeros);
-          pcv[l] = *reinterpret_cast<const uint2*>(cb);
+          for (int c = 0; c < 8; ++c) dpv[l][c] = buf_ld1(rp, vp, c * (HP * WP) * 4);
+          const u32x2 cv = __builtin_amdgcn_raw_buffer_load_b64(rc, ok ? co + wr * 8 : BUF_OOR, 0, 0);
+          pcv[l] = make_uint2(cv.x, cv.y);
         }
       }
     }
@@ -553,8 +698,9 @@ __device__ __forceinline__ void conv_fwd_split_body(FView in, FViewW out, FView 
   };
 
   // logical tile lt; xcd_tile() gives the physical one; past the last tile,
-  // tile ntiles lies beyond frame F and every lane reads paig_zeros (the
-  // prefetch stays unconditional: branch-free for the load counting)
+  // tile ntiles lies beyond frame F: its descriptor's extent is 0 and every
+  // lane reads 0 (the prefetch stays unconditional: branch-free for the load
+  // counting)
   // UPT: logical tile l of this block is band l % NRB of its (l / NRB)-th frame
   int lt = UPT ? 0 : bx;
   const int lstep = UPT ? 1 : gx;
@@ -567,16 +713,35 @@ __device__ __forceinline__ void conv_fwd_split_body(FView in, FViewW out, FView 
     }
   };
   issue(tile_of(lt));
+  // behind the prefetch's issue: LDS stores that no load is waited for (the
+  // halos), then the weight fragments (their loads are the oldest in flight).
+  // No barrier here: the halos and the fragments are first read after the
+  // first tile's commit barrier, and the fragments are never written again;
+  // the halos are, by every commit of UPT (its epilogue parks dX over the
+  // images) and of the fused upsample's SLA form (the window lies over the lo
+  // image), before that barrier.  The fused pool's first tile does no LDS
+  // work of its own
+  if constexpr (FORM > 0) zero_halo();
   if (PM == 0 && wp != nullptr) {
     // pre-split images of the whole COUT (paig_conv_wprep, once per step):
     // the channel exponents (header), then this slice's NT tiles of every
-    // k-step, coalesced 16-byte copies
-    constexpr int NTT = NT * C::NB, WLO = NS * NTT * 64, HDR = NTT * 16 * 4 / 16;
-    const int* hdr = reinterpret_cast<const int*>(wp);
+    // k-step, coalesced 16-byte copies: the rounds loaded at kernel entry,
+    // then the rest of a larger slice
+    constexpr int HDR = WHDR / 16;
+    if constexpr (WNE == 0) {
+      const int* hdr = reinterpret_cast<const int*>(wp);
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) ewn[nt] = hdr[co0 + nt * 16 + (lane & 15)];
+      for (int nt = 0; nt < NT; ++nt) ewn[nt] = hdr[co0 + nt * 16 + (lane & 15)];
+    }
+#pragma unroll
+    for (int k = 0; k < WNE; ++k) {
+      const int idx = tid + k * 256;
+      if (WSL % 256 != 0 && idx >= WSL) break;
+      *reinterpret_cast<s16x8*>(Wh + idx * 8) = wph[k];
+      *reinterpret_cast<s16x8*>(Wl + idx * 8) = wpl[k];
+    }
     const s16x8* img = wp + HDR;
-    for (int idx = tid; idx < NS * NT * 64; idx += 256) {
+    for (int idx = tid + WNE * 256; idx < WSL; idx += 256) {
       const int s = idx / (NT * 64), r = idx - s * (NT * 64);
       const int src = (s * NTT + blockIdx.y * NT) * 64 + r;
       *reinterpret_cast<s16x8*>(Wh + idx * 8) = img[src];
@@ -623,13 +788,15 @@ __device__ __forceinline__ void conv_fwd_split_body(FView in, FViewW out, FView 
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) tinv[nt] = __builtin_amdgcn_ldexpf(1.f, -ewn[nt]);
   }
-  // the bias of this lane's output channels (block constant)
-  float bvs[NT];
+  // the bias (loaded at kernel entry) has arrived before the loop: no wait
+  // on it behind a later prefetch
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
-    const int co = co0 + nt * 16 + (lane & 15);
-    bvs[nt] = *(bias && co < COUT ? bias + co : paig_zeros);
-    asm volatile("" ::"v"(bvs[nt]));   // arrived before the loop: no wait on it behind a prefetch
+    if constexpr (FORM == 0) {
+      const int co = co0 + nt * 16 + (lane & 15);
+      bvs[nt] = *(bias && co < COUT ? bias + co : paig_zeros);
+    }
+    asm volatile("" ::"v"(bvs[nt]));
   }
   // UPT: this thread's items (channel, source column) and their carried
   // partial sums of source rows kB (the tile's last) and kB + 1
@@ -637,20 +804,32 @@ __device__ __forceinline__ void conv_fwd_split_body(FView in, FViewW out, FView 
   float car0[NUI], car1[NUI];
   float auxu[UPT ? NUI : 1][UPT ? RT / 2 + 1 : 1];   // ReLU' inputs of the rows the tile completes
   // loaded before the tile's MFMAs (their latency hides behind them)
+  // (through a descriptor of the frame's source planes: this thread's item
+  // offsets less the row, once per block; rows outside the plane and idle
+  // lanes take BUF_OOR)
+  auto upt_unit = [&](int item) {
+    const int cl = item / WS2, j = item % WS2;
+    return (NCL * WS2) % 256 == 0 || item < NCL * WS2 ? ((co0 + cl) * ((H / 2) * WS2) + j) * 4 : BUF_OOR;
+  };
+  int avu[UPT && HOIST ? NUI : 1];
+  if constexpr (UPT && HOIST) {
+#pragma unroll
+    for (int u = 0; u < NUI; ++u) avu[u] = upt_unit(tid + u * 256);
+  }
   auto upt_aux = [&](int tile) {
     if constexpr (UPT) {
       if (flags & 2) {
         const int f = tile / NRB, kA = (tile % NRB) * (RT / 2);
+        const brsrc ra = tile_rsrc(aux.frame(f), aux.fs, 1, COUT * (H / 2) * WS2);
 #pragma unroll
         for (int u = 0; u < NUI; ++u) {
-          const int item = tid + u * 256;
-          const int cl = item / WS2, j = item % WS2;
-          const bool ok = (NCL * WS2) % 256 == 0 || item < NCL * WS2;
+          int vo;
+          if constexpr (HOIST) vo = avu[u];
+          else vo = upt_unit(opaque(tid) + u * 256);
 #pragma unroll
           for (int i = 0; i <= RT / 2; ++i) {
             const int k = kA - 1 + i;
-            const float* ap = aux.frame(f) + (long long)(co0 + cl) * ((H / 2) * WS2) + (long long)k * WS2 + j;
-            auxu[u][i] = *(ok && k >= 0 && k < H / 2 ? ap : paig_zeros);
+            auxu[u][i] = buf_ld1(ra, (unsigned)k < (unsigned)(H / 2) ? vo + k * WS2 * 4 : BUF_OOR, 0);
           }
         }
       }
@@ -724,6 +903,20 @@ __device__ __forceinline__ void conv_fwd_split_body(FView in, FViewW out, FView 
       car1[u] = P[RT / 2 + 1];
     }
   };
+  // AUXP: this lane's ReLU'-mask offsets inside the tile's frames, less the
+  // row origin and the 16-channel tile; lanes without an item are out of
+  // range from the start
+  constexpr bool AUXP = PAIG_FWD_AUXP && DG && C::VEC4 && !POOL && !UPT && MW * NT <= 8;
+  auto a_unit = [&](int wave, int ln, int mt) {
+    const int pix = fwd_mtile<MW, C::PO, POOL>(wave, mt) * 16 + (ln >> 4) * 4;
+    const int fi = pix / (RT * W), rem = pix % (RT * W);
+    return pix < C::TPXV ? ((FPT > 1 ? fi * (int)aux.fs : 0) + (co0 + (ln & 15)) * (int)HW + rem) * 4 : BUF_OOR;
+  };
+  int avo[AUXP && HOIST ? MW : 1];
+  if constexpr (AUXP && HOIST) {
+#pragma unroll
+    for (int mt = 0; mt < MW; ++mt) avo[mt] = a_unit(wv, lane, mt);
+  }
   for (;; lt += lstep) {
     const int tile = tile_of(lt);
     if (tile >= ntiles) break;
@@ -735,9 +928,8 @@ __device__ __forceinline__ void conv_fwd_split_body(FView in, FViewW out, FView 
     __syncthreads();
     // dgrad: this tile's ReLU' mask for the epilogue (AUXP), loaded before the
     // next tile's prefetch so that its latency hides behind the MFMAs
-    constexpr bool AUXP = PAIG_FWD_AUXP && DG && C::VEC4 && !POOL && !UPT && MW * NT <= 8;
     f32x4 auxv[AUXP ? MW : 1][AUXP ? NT : 1];
-    if constexpr (AUXP) {
+    if constexpr (AUXP && FORM == 0) {
       if (flags & 2) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
@@ -750,6 +942,21 @@ __device__ __forceinline__ void conv_fwd_split_body(FView in, FViewW out, FView 
             const bool ok = co < COUT && pix < C::TPXV && f < F;
             const float* ap = ok ? aux.frame(f) + co * HW + (long long)(y0 + rem / W) * W + rem % W : paig_zero_planes;
             auxv[mt][nt] = *reinterpret_cast<const f32x4*>(ap);
+          }
+        }
+      }
+    } else if constexpr (AUXP) {
+      if (flags & 2) {
+        const brsrc ra = tile_rsrc(aux.frame(f0), aux.fs, tile_nf(f0), COUT * (int)HW);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          const bool cok = co0 + nt * 16 + (lane & 15) < COUT;
+#pragma unroll
+          for (int mt = 0; mt < MW; ++mt) {
+            int vo;
+            if constexpr (HOIST) vo = avo[mt];
+            else vo = a_unit(opaque(wv), opaque(lane), mt);
+            auxv[mt][nt] = buf_ld4(ra, cok ? vo : BUF_OOR, (nt * 16 * (int)HW + y0 * W) * 4);
           }
         }
       }
@@ -1775,6 +1982,20 @@ static int sfwd_launch(FView in, FViewW out, FView aux, const float* w, const fl
   }
   if (PF) PAIG_REQUIRE(pout.p && pout.code, "conv split dgrad: the pool fold needs the pooled gradient and codes");
   else if (flags & 64) PAIG_REQUIRE(C::POOLOK && pout.p, "conv split fwd: no fused pool for Cin=%d Cout=%d H=%d", CIN, COUT, H);
+  // the prefetch addresses a tile's frames by 32-bit byte offsets from the
+  // tile's first frame (descriptors rebased per tile: no bound on F), within
+  // an extent below 2^31 bytes; a one-frame tile's extent does not depend on
+  // the strides.  Frames a short last tile does not have lie past the
+  // extent only if a frame's stride is at least its C x H x W
+  if constexpr (C::FPT > 1) {
+    constexpr long long SPAN = (1ll << 31) / (4 * (C::FPT - 1)) - 8 * 4096;
+    constexpr long long INF = (long long)CIN * (UPS ? (H / 2) * (W / 2) : H * W), HP2 = (H / 2) * (W / 2);
+    const bool mask = DG && (flags & 2) && aux.p;
+    PAIG_REQUIRE(in.fs >= INF && in.fs < SPAN && (!mask || (aux.fs >= (long long)COUT * H * W && aux.fs < SPAN)) &&
+                     (!PF || (pout.fs >= CIN * HP2 && pout.fs < SPAN && pout.code_fs >= C::CC * HP2 * 8 &&
+                              pout.code_fs < 4 * SPAN)),
+                 "conv split fwd: a frame stride is below the frame's size or does not fit the tile's 32-bit byte offsets");
+  }
   if constexpr (CIN == 3 && PM == 0 && !DG && !UPS && !UPT && !PF && C::NB == 1) {
     if (g_wpend_blocks && !(flags & 64)) {   // the deferred weight prep rides in this launch
       auto km = conv_fwd_wprep_k<CIN, COUT, H, W, KS, PM>;
