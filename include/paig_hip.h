@@ -31,7 +31,7 @@ extern "C" {
 /* Version of this interface: bumped whenever an entry point's argument list
  * or a data layout it exchanges changes (the Python binding refuses a library
  * of another version). */
-#define PAIG_ABI_VERSION 13
+#define PAIG_ABI_VERSION 14
 const char* paig_last_error(void);
 int paig_abi_version(void);
 /* f16 range guard of the split-precision path.  Activations and gradients
@@ -571,6 +571,43 @@ int paig_rollout_lstm_bwd(const float* dpos_roll, const float* dpvs, const float
                           const float* w_p, float half, float* dpos0, float* dvel0, float* dw_ih, float* dw_hh,
                           float* db_ih, float* db_hh, float* dw_p, float* db_p, int accumulate, void* ws,
                           size_t ws_bytes, int B, int D, int H, int R, void* stream);
+
+/* ---- interaction-network rollout cell: one relation network shared by all
+ *      ordered pairs of the K = D / 2 objects and one object network shared by
+ *      all objects, in the place of the physics equations, all R steps in one
+ *      launch.  Replaces stepping the two MLPs R times from Python inside the
+ *      reference's rollout loop physics_models.py:231-239 (a learned cell in
+ *      the place of cells.py; no reference counterpart):
+ *        s_i  = [(pos_i - half) / half, vel_i / half]   pos_i = pos[2i:2i+2]
+ *        e_ij = tanh(W_r2 tanh(W_r1 [s_i, s_j] + b_r1) + b_r2)    j != i
+ *        a_i  = sum_{j != i} e_ij                       in increasing j
+ *        y_i  = W_o2 tanh(W_o1 [s_i, a_i] + b_o1) + b_o2
+ *        pos_i' = pos_i + half y_i[:2];  vel_i' = vel_i + half y_i[2:]
+ *      w_r1 [H][8], b_r1 [H], w_r2 [H][H], b_r2 [H], w_o1 [H][4+H], b_o1 [H],
+ *      w_o2 [4][H], b_o2 [4]; pos0 / vel0 / pvs / dpos_roll / dpvs / dpos0 /
+ *      dvel0 as paig_rollout_fwd / _bwd (vel0 and dvel0 nullable).  D in
+ *      {4, 6}, H a multiple of 4 in [4, 128], a non-null ws of fewer than
+ *      paig_rollout_in_workspace bytes: PAIG_E_UNSUPPORTED.  Exact f32
+ *      products.  ws (16-byte aligned): the forward saves there what the
+ *      backward reads (per step the pair rows [s_i, s_j], both relation
+ *      activations, the object rows [s_i, a_i] and the object hidden
+ *      activation); a null ws saves nothing (inference) and gives the same
+ *      pvs bit for bit.  The backward (same ws, after that forward) walks
+ *      t = R .. 1 in one launch, leaves the four pre-activation adjoints in
+ *      ws and forms the eight parameter gradients from them with four
+ *      paig_gemm and four paig_colsum calls: no atomics, two runs are
+ *      bit-identical.  accumulate != 0 adds to the parameter gradients (as
+ *      paig_rollout_lstm_bwd); dpos0 / dvel0 are overwritten. */
+size_t paig_rollout_in_workspace(int B, int D, int H, int R);
+int paig_rollout_in_fwd(const float* pos0, long long pos0_ld, const float* vel0, const float* w_r1, const float* b_r1,
+                        const float* w_r2, const float* b_r2, const float* w_o1, const float* b_o1, const float* w_o2,
+                        const float* b_o2, float half, float* pvs, void* ws, size_t ws_bytes, int B, int D, int H,
+                        int R, void* stream);
+int paig_rollout_in_bwd(const float* dpos_roll, const float* dpvs, const float* w_r1, const float* w_r2,
+                        const float* w_o1, const float* w_o2, float half, float* dpos0, float* dvel0, float* dw_r1,
+                        float* db_r1, float* dw_r2, float* db_r2, float* dw_o1, float* db_o1, float* dw_o2,
+                        float* db_o2, int accumulate, void* ws, size_t ws_bytes, int B, int D, int H, int R,
+                        void* stream);
 
 /* ---- spatial-transformer decoder + compositing + per-frame SSE
  *      (conv_st_decoder physics_models.py:151-199, stn stn.py:5-16,

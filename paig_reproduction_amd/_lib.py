@@ -17,7 +17,7 @@ XMAX_SLOTS = 2048
 
 AB_PATH = os.environ.get("PAIG_AB_LIB")
 # include/paig_hip.h PAIG_ABI_VERSION: the SIGNATURES below are this version's
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -120,6 +120,9 @@ SIGNATURES = {
     "paig_rollout_lstm_workspace": (SZ, [I, I, I, I]),
     "paig_rollout_lstm_fwd": (I, [P, LL, P, P, P, P, P, P, P, F32, P, P, SZ, I, I, I, I, P]),
     "paig_rollout_lstm_bwd": (I, [P, P, P, P, P, F32, P, P, P, P, P, P, P, P, I, P, SZ, I, I, I, I, P]),
+    "paig_rollout_in_workspace": (SZ, [I, I, I, I]),
+    "paig_rollout_in_fwd": (I, [P, LL, P, P, P, P, P, P, P, P, P, F32, P, P, SZ, I, I, I, I, P]),
+    "paig_rollout_in_bwd": (I, [P, P, P, P, P, P, F32, P, P, P, P, P, P, P, P, P, P, I, P, SZ, I, I, I, I, P]),
     "paig_decoder_fwd": (I, [P, LL, LL, I, P, P, P, P, LL, P, LL, I, LL, P, I, I, I, I, P]),
     "paig_decoder_fwd_rollout": (I, [I, P, LL, P, P, P, P, P, I, I, I, P, LL, LL, I, P, P, P, P, LL, P, LL, I, LL, P, I, I,
                                       I, I, P]),
@@ -195,7 +198,8 @@ _QUERY = {"paig_last_error", "paig_abi_version", "paig_f16_range_status", "paig_
           "paig_gemm_parts_size", "paig_gemm_parts", "paig_unet_workspace", "paig_unet_workspace_ex",
           "paig_unet_buffer", "paig_unet_query", "paig_localiser_workspace",
           "paig_velmlp_rollout_bwd_workspace",
-          "paig_vfn_bwd_blocks", "paig_rollout_bwd_blocks", "paig_rollout_lstm_workspace", "paig_decoder_bwd_blocks", "paig_decoder_slab_len",
+          "paig_vfn_bwd_blocks", "paig_rollout_bwd_blocks", "paig_rollout_lstm_workspace", "paig_rollout_in_workspace",
+          "paig_decoder_bwd_blocks", "paig_decoder_slab_len",
           "paig_decoder_bwd_scratch", "paig_decoder_bwd_blocks_sigma", "paig_decoder_bwd_scratch_sigma",
           "paig_decoder_bwd_blocks_sigma_dev", "paig_decoder_bwd_scratch_sigma_dev",
           "paig_grad_norm_chunk", "paig_grad_norm_scratch"}

@@ -93,6 +93,7 @@ def live_steps(d_out, d_sse_roll, ent_roll):
 
 
 LSTM_CELL = 5   # Layout.cell of lstm_ode_cell (cells.lstm_ode_cell.KIND)
+IN_CELL = 6     # Layout.cell of interaction_ode_cell (cells.interaction_ode_cell.KIND)
 
 
 class Layout:
@@ -120,10 +121,13 @@ class Layout:
             self.F = frames
         self.alt_vel = model.alt_vel
         # paig_rollout_fwd's cell kinds (3, 4: the opt-in split-size-2 cells);
-        # 5: the black-box LSTM cell, on paig_rollout_lstm_fwd / _bwd
+        # 5: the black-box LSTM cell, on paig_rollout_lstm_fwd / _bwd;
+        # 6: the interaction-network cell, on paig_rollout_in_fwd / _bwd
         self.cell = {"spring_ode_cell": 0, "bouncing_ode_cell": 1, "gravity_ode_cell": 2, "spring2d_ode_cell": 3,
-                     "bouncing2d_ode_cell": 4, "lstm_ode_cell": LSTM_CELL}[model.cell_type]
+                     "bouncing2d_ode_cell": 4, "lstm_ode_cell": LSTM_CELL,
+                     "interaction_ode_cell": IN_CELL}[model.cell_type]
         self.lstm_H = model.rollout_cell.recurrent_units if self.cell == LSTM_CELL else 0
+        self.in_H = model.rollout_cell.recurrent_units if self.cell == IN_CELL else 0
         self.unet = self.H >= 40 if net is None else net == "unet"
         L = lib()
         self.net = 1 if self.unet else 0   # paig_unet_*: 0 ShallowUNet(hidden 8), 1 UNet(hidden 16)
@@ -283,6 +287,7 @@ class StepState:
     vel0: object = None         # forward: initial velocities, None when input_steps == 1; backward
     pvs: object = None          # forward: rollout positions and velocities; backward
     lstm_ws: object = None      # forward (lstm_ode_cell, a backward may follow): the cell's saved gates / states; backward
+    in_ws: object = None        # forward (interaction_ode_cell, a backward may follow): the cell's saved activations; backward
     wprep: dict = None          # _unet_forward: split weight images {(conv, kind): pointer}; _encoder_forward
     wprep_buf: object = None    # _unet_forward: the buffer behind wprep (kept alive)
     logits: object = None       # _unet_forward (head not fused): the U-Net's logits; mask softmax, _unet_backward
@@ -468,6 +473,12 @@ class Engine:
             ws = S.lstm_ws
             return (*pos0, *[ptr(p) for p in self.cell_params(lay)], float(lay.H / 2), ptr(S.pvs), ptr(ws),
                     ws.numel() * 4 if ws is not None else 0, lay.B, lay.D, lay.lstm_H, lay.R)
+        if lay.cell == IN_CELL:
+            # paig_rollout_in_fwd's: (pos0, ld, vel0, W_r1, b_r1, W_r2, b_r2,
+            # W_o1, b_o1, W_o2, b_o2, s, pvs, workspace, bytes, B, D, H, R)
+            ws = S.in_ws
+            return (*pos0, *[ptr(p) for p in self.cell_params(lay)], float(lay.H / 2), ptr(S.pvs), ptr(ws),
+                    ws.numel() * 4 if ws is not None else 0, lay.B, lay.D, lay.in_H, lay.R)
         dt, p0, p1 = self.cell_params(lay)
         return (lay.cell, *pos0, ptr(dt), ptr(p0), ptr(p1), ptr(S.pvs), lay.B, lay.D, lay.R)
 
@@ -504,7 +515,7 @@ class Engine:
         S.x_view = (ptr(x), lay.T * lay.frame, lay.Te, lay.frame) if lay.sequences else (ptr(x), lay.frame, 0, 0)
         return S
 
-    def forward(self, x, need_saved=True):
+    def forward(self, x, need_saved=True, grad_mode=True):
         require_device(x)
         model = self.model
         model._flat.ensure()
@@ -560,6 +571,8 @@ class Engine:
         S.pvs = _empty(B * (lay.R + 1) * 2 * D, dev)
         if lay.cell == LSTM_CELL and need_saved:   # what BPTT reads; inference saves nothing
             S.lstm_ws = _empty(L.paig_rollout_lstm_workspace(B, D, lay.lstm_H, lay.R) // 4, dev)
+        if lay.cell == IN_CELL and need_saved and grad_mode:   # not under no_grad (an evaluation forward)
+            S.in_ws = _empty(L.paig_rollout_in_workspace(B, D, lay.in_H, lay.R) // 4, dev)
         roll = self._rollout_args(S)
         vel_act = (ptr(S.Xv), ptr(S.v1), ptr(S.v2), ptr(S.vel0))
         dec = self._decoder_ops(S)
@@ -578,6 +591,9 @@ class Engine:
         if lay.cell == LSTM_CELL:   # the black-box cell: all R LSTM steps in one launch (never merged)
             with self._p("rollout_lstm_fwd"):
                 L.paig_rollout_lstm_fwd(*roll, st)
+        elif lay.cell == IN_CELL:   # the interaction-network cell: all R steps in one launch (never merged)
+            with self._p("rollout_in_fwd"):
+                L.paig_rollout_in_fwd(*roll, st)
         elif not merge_roll:   # the physics rollout (all R steps in one launch)
             L.paig_rollout_fwd(*roll, st)
         if not fuse_vfn:
@@ -792,7 +808,7 @@ class Engine:
 
     def cell_params(self, lay):
         m = self.model
-        if lay.cell == LSTM_CELL:   # (W_ih, W_hh, b_ih, b_hh, W_p, b_p): fp32, no dt
+        if lay.cell in (LSTM_CELL, IN_CELL):   # (W_ih, W_hh, b_ih, b_hh, W_p, b_p) / the eight of rel and obj: fp32, no dt
             return m.rollout_cell.weights()
         dt = m.rollout_cell.dt
         if lay.cell in (0, 3):
@@ -877,11 +893,20 @@ class Engine:
                 L.paig_rollout_lstm_bwd(ptr(dpos_roll), ptr(d_pvs), ptr(prm[0]), ptr(prm[1]), ptr(prm[4]),
                                         float(lay.H / 2), ptr(dpos0), ptr(dvel0), *[ptr(self.g(n)) for n in names], 0,
                                         ptr(S.lstm_ws), S.lstm_ws.numel() * 4, B, D, lay.lstm_H, R, st)
+        elif lay.cell == IN_CELL:
+            if S.in_ws is None:
+                raise PaigError("interaction_ode_cell: the forward saved no workspace for its backward")
+            names = ["rollout_cell." + n for n in ("rel.0.weight", "rel.0.bias", "rel.2.weight", "rel.2.bias",
+                                                   "obj.0.weight", "obj.0.bias", "obj.2.weight", "obj.2.bias")]
+            with self._p("rollout_in_bwd"):
+                L.paig_rollout_in_bwd(ptr(dpos_roll), ptr(d_pvs), ptr(prm[0]), ptr(prm[2]), ptr(prm[4]), ptr(prm[6]),
+                                      float(lay.H / 2), ptr(dpos0), ptr(dvel0), *[ptr(self.g(n)) for n in names], 0,
+                                      ptr(S.in_ws), S.in_ws.numel() * 4, B, D, lay.in_H, R, st)
         elif lay.cell in (0, 3):
             gk, gq = self.g("rollout_cell.k"), self.g("rollout_cell.equil")
         elif lay.cell == 2:
             gk = self.g("rollout_cell.g")
-        if lay.cell != LSTM_CELL:
+        if lay.cell not in (LSTM_CELL, IN_CELL):
             L.paig_rollout_bwd(lay.cell, ptr(S.pvs), ptr(dpos_roll), ptr(d_pvs), ptr(prm[0]), ptr(prm[1]), ptr(prm[2]),
                                ptr(dpos0), ptr(dvel0), ptr(rpart), ptr(gk), ptr(gq), 0, B, D, R, st)
         if S.vel0 is not None and lay.alt_vel:

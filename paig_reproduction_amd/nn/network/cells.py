@@ -14,7 +14,12 @@ fix of Q3: the same cells with split size 2, two objects in the plane.
 
 lstm_ode_cell is the black-box baseline (not in the reference, whose "lstm"
 table entry its rollout cannot call): a learned LSTM step in the place of the
-equations, on paig_rollout_lstm_fwd/bwd (csrc/rollout_lstm.hip)."""
+equations, on paig_rollout_lstm_fwd/bwd (csrc/rollout_lstm.hip).
+
+interaction_ode_cell is the object-centric learned baseline (not in the
+reference either): an interaction network, one relation MLP shared by all
+ordered pairs of objects and one object MLP shared by all objects, on
+paig_rollout_in_fwd/bwd (csrc/rollout_in.hip)."""
 import numpy as np
 import torch
 import torch.nn as tnn
@@ -130,5 +135,50 @@ class lstm_ode_cell(tnn.Module):
     def forward(self, poss, vels):
         """One step from a zero hidden state (paig_rollout_lstm_fwd/bwd with
         R = 1): poss, vels [B, D] -> (poss, vels)."""
+        from paig_reproduction_amd.nn.network import native_modules as _nm
+        return _nm.cell_forward(self, poss, vels)
+
+
+class interaction_ode_cell(tnn.Module):
+    """The interaction-network rollout cell: no equation, no dt, no hidden
+    state.  With K = input_size / 2 objects, s = frame side / 2 and
+    pos_i = pos[:, 2i:2i+2] (vel_i likewise), one step is
+
+        s_i  = [(pos_i - s) / s, vel_i / s]
+        e_ij = rel([s_i, s_j])                    every ordered pair j != i (receiver first)
+        a_i  = sum_{j != i} e_ij                  in increasing j
+        y_i  = obj([s_i, a_i]);  pos_i += s y_i[:2];  vel_i += s y_i[2:]
+
+    with rel = Linear(8, H), Tanh, Linear(H, H), Tanh and obj = Linear(4 + H,
+    H), Tanh, Linear(H, 4).  Torch's default initialisation; obj's last layer
+    is scaled by 0.1, so a fresh cell moves objects by about a pixel per
+    step.  Permutation-equivariant in the objects by construction."""
+    KIND = 6   # no kind of paig_rollout_fwd: paig_rollout_in_fwd / _bwd
+    H_MAX = 128
+
+    def __init__(self, input_size, hidden_size, recurrent_units=100, half=16.0):
+        super().__init__()
+        H = recurrent_units
+        if isinstance(H, bool) or not isinstance(H, int) or H % 4 != 0 or not 4 <= H <= self.H_MAX:
+            raise ValueError(f"interaction_ode_cell: recurrent_units={H!r} must be a multiple of 4 in [4, {self.H_MAX}]")
+        if input_size not in (4, 6):
+            raise ValueError(f"interaction_ode_cell: input_size={input_size!r}, 2 or 3 objects in the plane (4 or 6)")
+        self.input_size = input_size
+        self.hidden_size = hidden_size
+        self.recurrent_units = H
+        self.half = float(half)
+        self.rel = tnn.Sequential(tnn.Linear(8, H), tnn.Tanh(), tnn.Linear(H, H), tnn.Tanh())
+        self.obj = tnn.Sequential(tnn.Linear(4 + H, H), tnn.Tanh(), tnn.Linear(H, 4))
+        with torch.no_grad():
+            self.obj[2].weight.mul_(0.1)
+            self.obj[2].bias.mul_(0.1)
+
+    def weights(self):
+        """(W_r1, b_r1, W_r2, b_r2, W_o1, b_o1, W_o2, b_o2), the kernels' argument order."""
+        return (self.rel[0].weight, self.rel[0].bias, self.rel[2].weight, self.rel[2].bias, self.obj[0].weight,
+                self.obj[0].bias, self.obj[2].weight, self.obj[2].bias)
+
+    def forward(self, poss, vels):
+        """One step (paig_rollout_in_fwd/bwd with R = 1): poss, vels [B, D] -> (poss, vels)."""
         from paig_reproduction_amd.nn.network import native_modules as _nm
         return _nm.cell_forward(self, poss, vels)

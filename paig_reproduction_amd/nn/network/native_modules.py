@@ -6,6 +6,7 @@ nn/network/cells.py, nn/network/stn.py, callable one at a time):
   VelocityEncoder(inp)         blocks.py:31-49     paig_velmlp_* / paig_vel_pack + paig_gemm_ex
   <cell>(poss, vels)           cells.py:31-106     paig_rollout_fwd/bwd with R = 1
   lstm_ode_cell(poss, vels)    (no counterpart)    paig_rollout_lstm_fwd/bwd with R = 1
+  interaction_ode_cell(poss, vels)  (no counterpart)  paig_rollout_in_fwd/bwd with R = 1
   ShallowUNet / UNet (x)       blocks.py:278-308 / :172-237   the engine's U-Net plan
   ConvolutionalEncoder (inp)   blocks.py:77-103    the engine's encoder stage
   PhysicsNet.conv_st_decoder   physics_models.py:151-199      paig_vfn_* + paig_decoder_*
@@ -170,11 +171,58 @@ class _LstmCell(torch.autograd.Function):
         return dpos0, dvel0.view(D // 2, B, 2).permute(1, 0, 2).reshape(B, D), None, None
 
 
+class _InCell(torch.autograd.Function):
+    """interaction_ode_cell(poss, vels): paig_rollout_in_fwd / _bwd with R = 1."""
+
+    @staticmethod
+    def forward(ctx, pos, vel, anchor, cell):
+        pos, vel = _f32(pos), _f32(vel)
+        B, D = pos.shape
+        assert vel.shape == (B, D), (tuple(vel.shape), (B, D))
+        dev = pos.device
+        H = cell.recurrent_units
+        L = lib()
+        pvs = torch.empty(B, 2, 2 * D, device=dev)
+        vk = vel.view(B, D // 2, 2).permute(1, 0, 2).contiguous()
+        ws = None
+        if torch.is_grad_enabled() or ctx.needs_input_grad[2]:
+            ws = torch.empty(L.paig_rollout_in_workspace(B, D, H, 1) // 4, device=dev)
+        L.paig_rollout_in_fwd(ptr(pos), D, ptr(vk), *[ptr(p) for p in cell.weights()], cell.half, ptr(pvs), ptr(ws),
+                              ws.numel() * 4 if ws is not None else 0, B, D, H, 1, stream_handle(dev))
+        ctx.cell, ctx.ws, ctx.shape = cell, ws, (B, D, H)
+        return pvs[:, 1, :D].clone(), pvs[:, 1, D:].clone()
+
+    @staticmethod
+    def backward(ctx, dpos1, dvel1):
+        cell, ws = ctx.cell, ctx.ws
+        B, D, H = ctx.shape
+        if ws is None:
+            raise RuntimeError("interaction_ode_cell step was run without saving activations")
+        dev = ws.device
+        L = lib()
+        dpvs = torch.zeros(B, 2, 2 * D, device=dev)
+        if dpos1 is not None:
+            dpvs[:, 1, :D] = dpos1
+        if dvel1 is not None:
+            dpvs[:, 1, D:] = dvel1
+        dpos0, dvel0 = torch.empty(B, D, device=dev), torch.empty(B, D, device=dev)
+        W = cell.weights()
+        g = [torch.empty_like(p) for p in W]
+        L.paig_rollout_in_bwd(None, ptr(dpvs), ptr(W[0]), ptr(W[2]), ptr(W[4]), ptr(W[6]), cell.half, ptr(dpos0),
+                              ptr(dvel0), *[ptr(t) for t in g], 0, ptr(ws), ws.numel() * 4, B, D, H, 1,
+                              stream_handle(dev))
+        for p, t in zip(W, g):
+            deposit_grad(p, t)
+        return dpos0, dvel0.view(D // 2, B, 2).permute(1, 0, 2).reshape(B, D), None, None
+
+
 def cell_forward(cell, poss, vels):
     """<cell>.forward(poss, vels): 5 substeps (cells.py:31-51 / 60-83 / 96-106),
-    or one step of the black-box lstm_ode_cell."""
+    or one step of the black-box lstm_ode_cell or of interaction_ode_cell."""
     if cell.KIND == 5:
         return _LstmCell.apply(poss, vels, _anchor(), cell)
+    if cell.KIND == 6:
+        return _InCell.apply(poss, vels, _anchor(), cell)
     return _Cell.apply(poss, vels, _anchor(), cell)
 
 

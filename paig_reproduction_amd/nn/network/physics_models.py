@@ -25,7 +25,8 @@ from paig_reproduction_amd.flat import FlatParams
 from paig_reproduction_amd.nn.network.base import OPTIMIZERS, BaseNetTorch
 from paig_reproduction_amd.nn.network.blocks import ConvolutionalEncoder, VelocityEncoder, VariableFromNetwork
 from paig_reproduction_amd.nn.network.cells import (bouncing_ode_cell, spring_ode_cell, gravity_ode_cell,
-                                                    spring2d_ode_cell, bouncing2d_ode_cell, lstm_ode_cell)
+                                                    spring2d_ode_cell, bouncing2d_ode_cell, lstm_ode_cell,
+                                                    interaction_ode_cell)
 
 logger = logging.getLogger("tf")
 
@@ -38,6 +39,8 @@ CELLS = {
     "bouncing2d_ode_cell": bouncing2d_ode_cell,
     # opt-in (--blackbox_dynamics): a learned LSTM step in the place of the equations
     "lstm_ode_cell": lstm_ode_cell,
+    # opt-in (--interaction_dynamics): a learned interaction network in the place of the equations
+    "interaction_ode_cell": interaction_ode_cell,
     "lstm": pnn.LSTMCell,
 }
 
@@ -91,9 +94,12 @@ class _PhysicsStep(torch.autograd.Function):
     user gradient."""
 
     @staticmethod
-    def forward(ctx, anchor, x, engine):
+    def forward(ctx, anchor, x, engine, grad_mode=True):
+        # grad_mode: the caller's grad mode (inside a Function's forward it is
+        # always off); under no_grad no backward can follow, and the
+        # interaction cell then saves no activations
         need = ctx.needs_input_grad[0]
-        res, S = engine.forward(x, need_saved=need)
+        res, S = engine.forward(x, need_saved=need, grad_mode=grad_mode)
         ctx.engine = engine
         ctx.S = S
         ctx.hand = engine.last_loss_handoff = _LossHandoff()
@@ -146,7 +152,7 @@ class _PhysicsStep(torch.autograd.Function):
         no_roll = d_out is None and w_roll is None and lw_roll is None and d_pvs is None
         flat.end_backward(acc, ctx.engine.model.ROLLOUT_PARAMS if no_roll else ())
         ctx.S = None
-        return None, None, None
+        return None, None, None, None
 
 
 _LOSSW = {}
@@ -321,7 +327,7 @@ class PhysicsNet(BaseNetTorch):
         self.encoder = ConvolutionalEncoder(self.conv_input_shape, 200, 2, self.n_objs, self.device)
         self.velocity_encoder = VelocityEncoder(self.alt_vel, self.input_steps, self.n_objs, self.coord_units,
                                                 self.device)
-        if self.cell is lstm_ode_cell:
+        if self.cell in (lstm_ode_cell, interaction_ode_cell):
             self.rollout_cell = self.cell(self.coord_units // 2, self.coord_units // 2, recurrent_units,
                                           self.conv_input_shape[1] / 2)
         else:
@@ -368,6 +374,9 @@ class PhysicsNet(BaseNetTorch):
         elif self.cell_type == "lstm_ode_cell":   # fp32: the late part of the fp32 buffer, after every other name
             names += ["rollout_cell.lstm.weight_ih", "rollout_cell.lstm.weight_hh", "rollout_cell.lstm.bias_ih",
                       "rollout_cell.lstm.bias_hh", "rollout_cell.proj.weight", "rollout_cell.proj.bias"]
+        elif self.cell_type == "interaction_ode_cell":   # fp32, in the LSTM cell's place
+            names += ["rollout_cell." + n for n in ("rel.0.weight", "rel.0.bias", "rel.2.weight", "rel.2.bias",
+                                                    "obj.0.weight", "obj.0.bias", "obj.2.weight", "obj.2.bias")]
         return names
 
     def _init_native(self):
@@ -603,7 +612,7 @@ class PhysicsNet(BaseNetTorch):
         x = inp.detach()
         if x.dtype != torch.float32:
             x = x.float()
-        outs = _PhysicsStep.apply(self._anchor, x, eng)
+        outs = _PhysicsStep.apply(self._anchor, x, eng, torch.is_grad_enabled())
         (out, recons, enc_pos, pvs, sse_rec, sse_roll, priv_rec, priv_roll, masks, tmpl, cont, bg) = outs
         hand = eng.last_loss_handoff
         object.__setattr__(self, "_sse_priv", (priv_rec, priv_roll, (hand.rec, hand.roll)))

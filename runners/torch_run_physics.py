@@ -28,6 +28,10 @@ Additive flags only:
   --blackbox_dynamics            the black-box baseline: every task rolls out with lstm_ode_cell
         (nn.LSTMCell of --recurrent_units hidden units + a linear read-out, on the device) instead
         of its physics cell.  Off by default; an error together with --physics_2d.
+  --interaction_dynamics         the object-centric learned baseline: every task rolls out with
+        interaction_ode_cell (an interaction network: one relation MLP over all ordered pairs of
+        objects, one object MLP, --recurrent_units hidden units, on the device) instead of its
+        physics cell.  Off by default; an error together with --blackbox_dynamics or --physics_2d.
   --synthetic_device {0,1}       1: with --synthetic N and the task's npz missing,
         render the data on the GPU instead (nn/datasets/synth_device.py: HIP
         integrators + rasteriser) and keep it in HBM; no npz is written.  Same
@@ -144,6 +148,10 @@ def build_parser():
                    help="the black-box baseline: every task rolls out with lstm_ode_cell (an LSTM of "
                         "--recurrent_units hidden units and a linear read-out) instead of its physics cell; "
                         "not with --physics_2d")
+    p.add_argument("--interaction_dynamics", action="store_true",
+                   help="the object-centric learned baseline: every task rolls out with interaction_ode_cell (an "
+                        "interaction network of --recurrent_units hidden units) instead of its physics cell; not "
+                        "with --blackbox_dynamics or --physics_2d")
     return p
 
 
@@ -154,7 +162,13 @@ CELLS_2D = {"spring_ode_cell": "spring2d_ode_cell", "bouncing_ode_cell": "bounci
 def task_cell(args):
     """The rollout cell of args.task: TASKS' preset, or under --physics_2d its
     2-D class (an error for a task whose cell has none), or under
-    --blackbox_dynamics the learned lstm_ode_cell for every task."""
+    --blackbox_dynamics / --interaction_dynamics the learned lstm_ode_cell /
+    interaction_ode_cell for every task."""
+    if getattr(args, "interaction_dynamics", False):
+        if getattr(args, "blackbox_dynamics", False) or args.physics_2d:
+            raise SystemExit("--interaction_dynamics replaces the physics cell: it cannot be combined with "
+                             "--blackbox_dynamics or --physics_2d")
+        return "interaction_ode_cell"
     if getattr(args, "blackbox_dynamics", False):
         if args.physics_2d:
             raise SystemExit("--blackbox_dynamics replaces the physics cell: it cannot be combined with --physics_2d")
@@ -221,6 +235,9 @@ def main(argv=None):
     if args.blackbox_dynamics and args.physics_lr_mult != 1.0:
         logger.warning("--physics_lr_mult %g has no effect with --blackbox_dynamics: lstm_ode_cell has no fp64 "
                        "physics parameter, its weights step with --base_lr", args.physics_lr_mult)
+    if args.interaction_dynamics and args.physics_lr_mult != 1.0:
+        logger.warning("--physics_lr_mult %g has no effect with --interaction_dynamics: interaction_ode_cell has no "
+                       "fp64 physics parameter, its weights step with --base_lr", args.physics_lr_mult)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
