@@ -60,7 +60,7 @@ int paig_localiser_fwd(const float* x1, const float* W1, const float* b1, const 
   float* w2t = reinterpret_cast<float*>(base + c256(paig_gemm_parts_size(KF, IN, n1, math) * 4));
   const int S = paig_gemm_parts(0, 1, KF, IN, n1, x1, n1, W1, n1, part, paig_gemm_parts_size(KF, IN, n1, math), math,
                                 stream);
-  if (S <= 0) return S < 0 ? S : PAIG_E_SHAPE;
+  if (S <= 0) return S < 0 ? -S : PAIG_E_SHAPE;   // (a negative S is paig_gemm_parts's status, negated)
   return paig_dense_tail_fwd(part, S, b1, h1, W2, w2t, b2, h2, W3, b3, h3, pos, F, K, IN, half, stream);
 }
 

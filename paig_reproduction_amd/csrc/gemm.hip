@@ -1104,8 +1104,10 @@ size_t paig_gemm_parts_size(int M, int N, int K, int math) {
   return (size_t)(p.S > 1 ? p.S : 1) * M * N;
 }
 
-int paig_gemm_parts(int ta, int tb, int M, int N, int K, const float* A, long long lda, const float* B,
-                    long long ldb, float* part, size_t part_floats, int math, void* stream) {
+// paig_gemm_parts with the slab count in *S_out and the usual status (0, a
+// PAIG_E_* code or a hipError_t: positive, so never to be returned as a count)
+static int gemm_parts_launch(int ta, int tb, int M, int N, int K, const float* A, long long lda, const float* B,
+                             long long ldb, float* part, size_t part_floats, int math, void* stream, int* S_out) {
   hipStream_t st = (hipStream_t)stream;
   if (int rc = paig_gemm_flush(stream)) return rc;   // (a deferred epilogue runs first)
   PAIG_REQUIRE(math >= 0 && math <= 6, "paig_gemm_parts: math must be 0..6, got %d", math);
@@ -1130,7 +1132,15 @@ int paig_gemm_parts(int ta, int tb, int M, int N, int K, const float* A, long lo
   else PAIG_G(false, false);
 #undef PAIG_G
   PAIG_CHECK_LAUNCH();
-  return S;
+  *S_out = S;
+  return 0;
+}
+
+int paig_gemm_parts(int ta, int tb, int M, int N, int K, const float* A, long long lda, const float* B,
+                    long long ldb, float* part, size_t part_floats, int math, void* stream) {
+  int S = 0;
+  const int rc = gemm_parts_launch(ta, tb, M, N, K, A, lda, B, ldb, part, part_floats, math, stream, &S);
+  return rc ? -rc : S;   // a failure is a negative status: a positive return is always the slab count
 }
 
 int paig_gemm_ex(int ta, int tb, int M, int N, int K, float alpha, const float* A, long long lda, const float* B,
