@@ -27,18 +27,14 @@
 // Products are exact f32 (v_mfma_f32_16x16x4_f32).
 #include <algorithm>
 
-#include "common.h"
+#include "rollout_learned.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int IN_HMAX = 128;   // hidden units (8 waves of 16)
 constexpr int IN_ROWS = 16;    // sequences per block
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
+static_assert(IN_ROWS == LEARNED_ROWS, "the grid of LEARNED_DISPATCH");
 
 // the saved state of one forward (floats from the workspace base), then the
 // backward's own buffers; every region a multiple of 4 floats.  Row of a
@@ -435,21 +431,6 @@ static int in_ws_ok(const char* who, const void* ws, size_t ws_bytes, const InWs
   return 0;
 }
 
-// KH bucket of H: the smallest instantiated count of hidden k-steps >= H / 4
-#define IN_DISPATCH(KERNEL, ...)                                                                           \
-  do {                                                                                                     \
-    const int kh = H / 4;                                                                                  \
-    const dim3 grid(cdiv(B, IN_ROWS)), block(64 * cdiv(H, 16));                                            \
-    if (D == 4 && kh <= 8) hipLaunchKernelGGL((KERNEL<2, 8>), grid, block, 0, st, __VA_ARGS__);            \
-    else if (D == 4 && kh <= 16) hipLaunchKernelGGL((KERNEL<2, 16>), grid, block, 0, st, __VA_ARGS__);     \
-    else if (D == 4 && kh <= 25) hipLaunchKernelGGL((KERNEL<2, 25>), grid, block, 0, st, __VA_ARGS__);     \
-    else if (D == 4) hipLaunchKernelGGL((KERNEL<2, 32>), grid, block, 0, st, __VA_ARGS__);                 \
-    else if (kh <= 8) hipLaunchKernelGGL((KERNEL<3, 8>), grid, block, 0, st, __VA_ARGS__);                 \
-    else if (kh <= 16) hipLaunchKernelGGL((KERNEL<3, 16>), grid, block, 0, st, __VA_ARGS__);               \
-    else if (kh <= 25) hipLaunchKernelGGL((KERNEL<3, 25>), grid, block, 0, st, __VA_ARGS__);               \
-    else hipLaunchKernelGGL((KERNEL<3, 32>), grid, block, 0, st, __VA_ARGS__);                             \
-  } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -476,8 +457,8 @@ int paig_rollout_in_fwd(const float* pos0, long long pos0_ld, const float* vel0,
     float* f = (float*)ws;
     xr = f + L.xr, h1 = f + L.h1, e = f + L.e, xo = f + L.xo, ho = f + L.ho;
   }
-  IN_DISPATCH(in_fwd_k, pos0, pos0_ld, vel0, w_r1, b_r1, w_r2, b_r2, w_o1, b_o1, w_o2, b_o2, half, pvs, xr, h1, e, xo,
-              ho, B, H, R);
+  LEARNED_DISPATCH(in_fwd_k, pos0, pos0_ld, vel0, w_r1, b_r1, w_r2, b_r2, w_o1, b_o1, w_o2, b_o2, half, pvs, xr, h1, e,
+                   xo, ho, B, H, R);
   PAIG_CHECK_LAUNCH();
   return 0;
 }
@@ -498,25 +479,17 @@ int paig_rollout_in_bwd(const float* dpos_roll, const float* dpvs, const float* 
   if (int rc = in_ws_ok("paig_rollout_in_bwd", ws, ws_bytes, L)) return rc;
   float* f = (float*)ws;
   float *dz1 = f + L.dz1, *dz2 = f + L.dz2, *dzo = f + L.dzo, *dy = f + L.dy;
-  IN_DISPATCH(in_bwd_k, dpos_roll, dpvs, w_r1, w_r2, w_o1, w_o2, half, f + L.h1, f + L.e, f + L.ho, dz1, dz2, dzo, dy,
-              dpos0, dvel0, B, H, R);
+  LEARNED_DISPATCH(in_bwd_k, dpos_roll, dpvs, w_r1, w_r2, w_o1, w_o2, half, f + L.h1, f + L.e, f + L.ho, dz1, dz2, dzo,
+                   dy, dpos0, dvel0, B, H, R);
   PAIG_CHECK_LAUNCH();
   // ---- weight gradients: sums over all pair / object rows, off the serial chain
   const int K = D / 2, pr = B * R * K * (K - 1), orows = B * R * K, HO = 4 + H;
   const float beta = accumulate ? 1.f : 0.f;
   int rc;
-  if ((rc = paig_gemm(1, 0, H, 8, pr, 1.f, dz1, H, f + L.xr, 8, beta, dw_r1, 8, nullptr, 0, 0, nullptr, 0, nullptr,
-                      f + L.gemm, L.gemm_floats, stream)))
-    return rc;
-  if ((rc = paig_gemm(1, 0, H, H, pr, 1.f, dz2, H, f + L.h1, H, beta, dw_r2, H, nullptr, 0, 0, nullptr, 0, nullptr,
-                      f + L.gemm, L.gemm_floats, stream)))
-    return rc;
-  if ((rc = paig_gemm(1, 0, H, HO, orows, 1.f, dzo, H, f + L.xo, HO, beta, dw_o1, HO, nullptr, 0, 0, nullptr, 0, nullptr,
-                      f + L.gemm, L.gemm_floats, stream)))
-    return rc;
-  if ((rc = paig_gemm(1, 0, 4, H, orows, 1.f, dy, 4, f + L.ho, H, beta, dw_o2, H, nullptr, 0, 0, nullptr, 0, nullptr,
-                      f + L.gemm, L.gemm_floats, stream)))
-    return rc;
+  if ((rc = learned_wgrad(H, 8, pr, dz1, f + L.xr, beta, dw_r1, f + L.gemm, L.gemm_floats, stream))) return rc;
+  if ((rc = learned_wgrad(H, H, pr, dz2, f + L.h1, beta, dw_r2, f + L.gemm, L.gemm_floats, stream))) return rc;
+  if ((rc = learned_wgrad(H, HO, orows, dzo, f + L.xo, beta, dw_o1, f + L.gemm, L.gemm_floats, stream))) return rc;
+  if ((rc = learned_wgrad(4, H, orows, dy, f + L.ho, beta, dw_o2, f + L.gemm, L.gemm_floats, stream))) return rc;
   // ---- bias gradients: column sums in a fixed order
   if ((rc = paig_colsum(dz1, pr, H, H, db_r1, accumulate, f + L.colsum, stream))) return rc;
   if ((rc = paig_colsum(dz2, pr, H, H, db_r2, accumulate, f + L.colsum, stream))) return rc;

@@ -26,18 +26,14 @@
 // Products are exact f32 (v_mfma_f32_16x16x4_f32).
 #include <algorithm>
 
-#include "common.h"
+#include "rollout_learned.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int LSTM_HMAX = 128;   // hidden units (8 waves of 16)
 constexpr int LSTM_ROWS = 16;    // sequences per block
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
+static_assert(LSTM_ROWS == LEARNED_ROWS, "the grid of LEARNED_DISPATCH");
 // finite for every finite x: exp(-x) = inf gives 1 / inf = 0
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -338,21 +334,6 @@ static int lstm_shape_ok(const char* who, int B, int D, int H, int R) {
   return 0;
 }
 
-// KH bucket of H: the smallest instantiated count of h k-steps >= H / 4
-#define LSTM_DISPATCH(KERNEL, ...)                                                                           \
-  do {                                                                                                       \
-    const int kh = H / 4;                                                                                    \
-    const dim3 grid(cdiv(B, LSTM_ROWS)), block(64 * cdiv(H, 16));                                            \
-    if (D == 4 && kh <= 8) hipLaunchKernelGGL((KERNEL<2, 8>), grid, block, 0, st, __VA_ARGS__);              \
-    else if (D == 4 && kh <= 16) hipLaunchKernelGGL((KERNEL<2, 16>), grid, block, 0, st, __VA_ARGS__);       \
-    else if (D == 4 && kh <= 25) hipLaunchKernelGGL((KERNEL<2, 25>), grid, block, 0, st, __VA_ARGS__);       \
-    else if (D == 4) hipLaunchKernelGGL((KERNEL<2, 32>), grid, block, 0, st, __VA_ARGS__);                   \
-    else if (kh <= 8) hipLaunchKernelGGL((KERNEL<3, 8>), grid, block, 0, st, __VA_ARGS__);                   \
-    else if (kh <= 16) hipLaunchKernelGGL((KERNEL<3, 16>), grid, block, 0, st, __VA_ARGS__);                 \
-    else if (kh <= 25) hipLaunchKernelGGL((KERNEL<3, 25>), grid, block, 0, st, __VA_ARGS__);                 \
-    else hipLaunchKernelGGL((KERNEL<3, 32>), grid, block, 0, st, __VA_ARGS__);                               \
-  } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -380,7 +361,8 @@ int paig_rollout_lstm_fwd(const float* pos0, long long pos0_ld, const float* vel
     float* f = (float*)ws;
     g = f + L.gates, c = f + L.c, hn = f + L.hn, hp = f + L.hp, x = f + L.x;
   }
-  LSTM_DISPATCH(lstm_fwd_k, pos0, pos0_ld, vel0, w_ih, w_hh, b_ih, b_hh, w_p, b_p, half, pvs, g, c, hn, hp, x, B, H, R);
+  LEARNED_DISPATCH(lstm_fwd_k, pos0, pos0_ld, vel0, w_ih, w_hh, b_ih, b_hh, w_p, b_p, half, pvs, g, c, hn, hp, x, B, H,
+                   R);
   PAIG_CHECK_LAUNCH();
   return 0;
 }
@@ -401,21 +383,16 @@ int paig_rollout_lstm_bwd(const float* dpos_roll, const float* dpvs, const float
                L.total * sizeof(float));
   float* f = (float*)ws;
   float *dz = f + L.dz, *dy = f + L.dy;
-  LSTM_DISPATCH(lstm_bwd_k, dpos_roll, dpvs, w_ih, w_hh, w_p, half, f + L.gates, f + L.c, dz, dy, dpos0, dvel0, B, H, R);
+  LEARNED_DISPATCH(lstm_bwd_k, dpos_roll, dpvs, w_ih, w_hh, w_p, half, f + L.gates, f + L.c, dz, dy, dpos0, dvel0, B, H,
+                   R);
   PAIG_CHECK_LAUNCH();
   // ---- weight gradients: sums over all B R rows, off the serial chain
   const int rows = B * R, H4 = 4 * H, D2 = 2 * D;
   const float beta = accumulate ? 1.f : 0.f;
   int rc;
-  if ((rc = paig_gemm(1, 0, H4, D2, rows, 1.f, dz, H4, f + L.x, D2, beta, dw_ih, D2, nullptr, 0, 0, nullptr, 0, nullptr,
-                      f + L.gemm, L.gemm_floats, stream)))
-    return rc;
-  if ((rc = paig_gemm(1, 0, H4, H, rows, 1.f, dz, H4, f + L.hp, H, beta, dw_hh, H, nullptr, 0, 0, nullptr, 0, nullptr,
-                      f + L.gemm, L.gemm_floats, stream)))
-    return rc;
-  if ((rc = paig_gemm(1, 0, D2, H, rows, 1.f, dy, D2, f + L.hn, H, beta, dw_p, H, nullptr, 0, 0, nullptr, 0, nullptr,
-                      f + L.gemm, L.gemm_floats, stream)))
-    return rc;
+  if ((rc = learned_wgrad(H4, D2, rows, dz, f + L.x, beta, dw_ih, f + L.gemm, L.gemm_floats, stream))) return rc;
+  if ((rc = learned_wgrad(H4, H, rows, dz, f + L.hp, beta, dw_hh, f + L.gemm, L.gemm_floats, stream))) return rc;
+  if ((rc = learned_wgrad(D2, H, rows, dy, f + L.hn, beta, dw_p, f + L.gemm, L.gemm_floats, stream))) return rc;
   // ---- bias gradients: column sums in a fixed order
   if ((rc = paig_colsum(dz, rows, H4, H4, db_ih, accumulate, f + L.colsum, stream))) return rc;
   if ((rc = paig_colsum(dz, rows, H4, H4, db_hh, accumulate, f + L.colsum, stream))) return rc;

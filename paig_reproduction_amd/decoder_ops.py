@@ -94,7 +94,7 @@ class DecoderOps:
     def fwd(self, pos_view, out, out_fs, targets, sse, F, st, roll=None):
         """Decode F frames at pos_view (pointer, outer, inner, group) into out,
         with their SSE against targets into sse.  roll: the rollout's
-        arguments (engine._rollout_args) to run it in the same launch."""
+        arguments (RolloutOps.merged_args) to run it in the same launch."""
         kind = targets.kind
         if kind != "none" and sse is None:
             raise PaigError("decoder fwd: targets without an SSE output")

@@ -27,6 +27,7 @@ import torch
 
 from ._lib import PaigError, lib, ptr, stream_handle, require_device
 from .decoder_ops import DecoderOps, Sigma, Targets
+from .rollout_ops import SPECS, RolloutOps
 
 # The U-Net plans (ShallowUNet blocks.py:240-308, UNet :106-237: buffers,
 # ops, which upsamples / pools fuse into which convs, the backward's
@@ -92,10 +93,6 @@ def live_steps(d_out, d_sse_roll, ent_roll):
     return 0
 
 
-LSTM_CELL = 5   # Layout.cell of lstm_ode_cell (cells.lstm_ode_cell.KIND)
-IN_CELL = 6     # Layout.cell of interaction_ode_cell (cells.interaction_ode_cell.KIND)
-
-
 class Layout:
     """Static shapes of one step (from the PhysicsNet config and batch)."""
 
@@ -120,14 +117,8 @@ class Layout:
         else:
             self.F = frames
         self.alt_vel = model.alt_vel
-        # paig_rollout_fwd's cell kinds (3, 4: the opt-in split-size-2 cells);
-        # 5: the black-box LSTM cell, on paig_rollout_lstm_fwd / _bwd;
-        # 6: the interaction-network cell, on paig_rollout_in_fwd / _bwd
-        self.cell = {"spring_ode_cell": 0, "bouncing_ode_cell": 1, "gravity_ode_cell": 2, "spring2d_ode_cell": 3,
-                     "bouncing2d_ode_cell": 4, "lstm_ode_cell": LSTM_CELL,
-                     "interaction_ode_cell": IN_CELL}[model.cell_type]
-        self.lstm_H = model.rollout_cell.recurrent_units if self.cell == LSTM_CELL else 0
-        self.in_H = model.rollout_cell.recurrent_units if self.cell == IN_CELL else 0
+        self.spec = SPECS[model.cell_type]   # the rollout cell's kernels, operands and parameter names
+        self.cell = self.spec.kind
         self.unet = self.H >= 40 if net is None else net == "unet"
         L = lib()
         self.net = 1 if self.unet else 0   # paig_unet_*: 0 ShallowUNet(hidden 8), 1 UNet(hidden 16)
@@ -286,8 +277,7 @@ class StepState:
     v2: object = None           # forward: velocity MLP hidden 2; backward
     vel0: object = None         # forward: initial velocities, None when input_steps == 1; backward
     pvs: object = None          # forward: rollout positions and velocities; backward
-    lstm_ws: object = None      # forward (lstm_ode_cell, a backward may follow): the cell's saved gates / states; backward
-    in_ws: object = None        # forward (interaction_ode_cell, a backward may follow): the cell's saved activations; backward
+    roll_ws: object = None      # forward (a learned cell, a backward may follow): the cell's saved activations; backward
     wprep: dict = None          # _unet_forward: split weight images {(conv, kind): pointer}; _encoder_forward
     wprep_buf: object = None    # _unet_forward: the buffer behind wprep (kept alive)
     logits: object = None       # _unet_forward (head not fused): the U-Net's logits; mask softmax, _unet_backward
@@ -382,7 +372,9 @@ class Engine:
     def _p(self, tag, flops=0, nbytes=0):
         """Probe context of one launch: algorithmic FLOPs and HBM bytes (the
         compulsory operand reads + result writes) for bench.py's roofline."""
-        return self.probe.wrap(tag, flops, nbytes) if self.probe is not None else _NOPROBE
+        if self.probe is None or tag is None:   # (no tag: an unlabelled launch)
+            return _NOPROBE
+        return self.probe.wrap(tag, flops, nbytes)
 
     # -- parameter access ------------------------------------------------
     def p(self, name):
@@ -462,25 +454,9 @@ class Engine:
                   for suf in (".l1.weight", ".l1.bias", ".l2.weight", ".l2.bias")],
                 _parr([ptr(pt) for pt in vparts]), _iarr(P))
 
-    def _rollout_args(self, S):
-        """(cell, pos0, ld, vel0, dt, p0, p1, pvs, B, D, R): the rollout starts
-        at the last input step's encoded positions."""
-        lay = S.lay
-        pos0 = (ptr(S.enc_pos) + (lay.ins - 1) * lay.D * 4, lay.Te * lay.D, ptr(S.vel0))
-        if lay.cell == LSTM_CELL:
-            # paig_rollout_lstm_fwd's: (pos0, ld, vel0, W_ih, W_hh, b_ih, b_hh,
-            # W_p, b_p, s, pvs, workspace, bytes, B, D, H, R)
-            ws = S.lstm_ws
-            return (*pos0, *[ptr(p) for p in self.cell_params(lay)], float(lay.H / 2), ptr(S.pvs), ptr(ws),
-                    ws.numel() * 4 if ws is not None else 0, lay.B, lay.D, lay.lstm_H, lay.R)
-        if lay.cell == IN_CELL:
-            # paig_rollout_in_fwd's: (pos0, ld, vel0, W_r1, b_r1, W_r2, b_r2,
-            # W_o1, b_o1, W_o2, b_o2, s, pvs, workspace, bytes, B, D, H, R)
-            ws = S.in_ws
-            return (*pos0, *[ptr(p) for p in self.cell_params(lay)], float(lay.H / 2), ptr(S.pvs), ptr(ws),
-                    ws.numel() * 4 if ws is not None else 0, lay.B, lay.D, lay.in_H, lay.R)
-        dt, p0, p1 = self.cell_params(lay)
-        return (lay.cell, *pos0, ptr(dt), ptr(p0), ptr(p1), ptr(S.pvs), lay.B, lay.D, lay.R)
+    def _rollout_ops(self, lay):
+        """The rollout calls of the model's cell at this step's shape."""
+        return RolloutOps(self.L, self.model.rollout_cell, lay.B, lay.D, lay.R, float(lay.H / 2))
 
     def _decoder_ops(self, S):
         """The decoder calls of this forward's sigma and VFN sources."""
@@ -569,11 +545,11 @@ class Engine:
                 S.v1 = _empty(K * B * 100, dev)
                 S.v2 = _empty(K * B * 100, dev)
         S.pvs = _empty(B * (lay.R + 1) * 2 * D, dev)
-        if lay.cell == LSTM_CELL and need_saved:   # what BPTT reads; inference saves nothing
-            S.lstm_ws = _empty(L.paig_rollout_lstm_workspace(B, D, lay.lstm_H, lay.R) // 4, dev)
-        if lay.cell == IN_CELL and need_saved and grad_mode:   # not under no_grad (an evaluation forward)
-            S.in_ws = _empty(L.paig_rollout_in_workspace(B, D, lay.in_H, lay.R) // 4, dev)
-        roll = self._rollout_args(S)
+        rops = self._rollout_ops(lay)
+        if lay.spec.saves(need_saved, grad_mode):
+            S.roll_ws = _empty(rops.workspace_floats(), dev)
+        # (pos0, ld, vel0, pvs): the rollout starts at the last input step's encoded positions
+        roll = (ptr(enc_pos) + (lay.ins - 1) * D * 4, lay.Te * D, ptr(S.vel0), ptr(S.pvs))
         vel_act = (ptr(S.Xv), ptr(S.v1), ptr(S.v2), ptr(S.vel0))
         dec = self._decoder_ops(S)
         # velocity MLP + VFN sources in one launch (independent); then the
@@ -588,20 +564,15 @@ class Engine:
             self.linear(S.Xv, K * B, "velocity_encoder.init_vel_linear", S.vel0, 0, st, ws)
         elif S.vel0 is not None:   # the whole MLP (packing fused) in one launch
             L.paig_velmlp_fwd(ptr(enc_pos), B, lay.Te, K, lay.ins, *self._velmlp_params(), *vel_act, st)
-        if lay.cell == LSTM_CELL:   # the black-box cell: all R LSTM steps in one launch (never merged)
-            with self._p("rollout_lstm_fwd"):
-                L.paig_rollout_lstm_fwd(*roll, st)
-        elif lay.cell == IN_CELL:   # the interaction-network cell: all R steps in one launch (never merged)
-            with self._p("rollout_in_fwd"):
-                L.paig_rollout_in_fwd(*roll, st)
-        elif not merge_roll:   # the physics rollout (all R steps in one launch)
-            L.paig_rollout_fwd(*roll, st)
+        if not merge_roll:   # all R steps in one launch (a learned cell never merges: _ROLL_REC has none)
+            with self._p(lay.spec.family.probe_fwd):
+                rops.fwd(*roll, S.roll_ws, st)
         if not fuse_vfn:
             L.paig_vfn_fwd_multi(*self._vfn_fwd_args(S), st)
         # reconstruction decode (all B*Te frames, SSE vs input fused)
         with self._p("dec_fwd:recon+rollout" if merge_roll else "dec_fwd:recon", 0, self._dec_bytes(F, lay)):
             dec.fwd((ptr(enc_pos), 0, 2 * K, 0), ptr(recons), lay.frame, S.tgt_rec, ptr(sse_rec), F, st,
-                    roll=roll if merge_roll else None)
+                    roll=rops.merged_args(*roll) if merge_roll else None)
 
         # ---- rollout decode (all B*R frames in one launch, SSE vs input[:, ins:])
         out = _empty(B * lay.R * lay.frame, dev)
@@ -806,17 +777,6 @@ class Engine:
                                       ptr(enc_pos), F, K, 200, float(H / 2), st)
         S.masks, S.objs, S.l1_x, S.h1, S.h2, S.h3, S.enc_pos = masks, objs, l1_x, h1, h2, h3, enc_pos
 
-    def cell_params(self, lay):
-        m = self.model
-        if lay.cell in (LSTM_CELL, IN_CELL):   # (W_ih, W_hh, b_ih, b_hh, W_p, b_p) / the eight of rel and obj: fp32, no dt
-            return m.rollout_cell.weights()
-        dt = m.rollout_cell.dt
-        if lay.cell in (0, 3):
-            return dt, m.rollout_cell.k, m.rollout_cell.equil
-        if lay.cell == 2:
-            return dt, m.rollout_cell.g, m.rollout_cell.m
-        return dt, None, None
-
     # -- backward --------------------------------------------------------
     def backward(self, S, d_sse_rec=None, d_sse_roll=None, d_out=None, d_recons=None, d_enc_pos=None, d_pvs=None,
                  roll_live=0, lossw=None):
@@ -861,7 +821,8 @@ class Engine:
         dsrc = _empty(slab_len, dev)
         dpos0 = _empty(B * D, dev)
         dvel0 = _empty(K * B * 2, dev) if S.vel0 is not None else None
-        rpart = _empty(2 * L.paig_rollout_bwd_blocks(B), dev, torch.float64)
+        rops = self._rollout_ops(lay)
+        rpart = _empty(rops.part_doubles(), dev, torch.float64)
         dXv = vslab = None
         if S.vel0 is not None:
             dXv = _empty(K * B * 2 * (lay.ins - 1 if lay.alt_vel else lay.ins), dev)
@@ -882,33 +843,11 @@ class Engine:
                     ptr(dpos_roll), ptr(slab) + nb_rec * slab_len * 4, ptr(scratch), B * R, roll_live, st, dsig_roll)
 
         # ---- rollout adjoint -> d pos0, d vel0, physics params; velocity encoder backward
-        prm = self.cell_params(lay)
-        gk = gq = None
-        if lay.cell == LSTM_CELL:
-            if S.lstm_ws is None:
-                raise PaigError("lstm_ode_cell: the forward saved no workspace for its backward")
-            names = ["rollout_cell." + n for n in ("lstm.weight_ih", "lstm.weight_hh", "lstm.bias_ih", "lstm.bias_hh",
-                                                   "proj.weight", "proj.bias")]
-            with self._p("rollout_lstm_bwd"):
-                L.paig_rollout_lstm_bwd(ptr(dpos_roll), ptr(d_pvs), ptr(prm[0]), ptr(prm[1]), ptr(prm[4]),
-                                        float(lay.H / 2), ptr(dpos0), ptr(dvel0), *[ptr(self.g(n)) for n in names], 0,
-                                        ptr(S.lstm_ws), S.lstm_ws.numel() * 4, B, D, lay.lstm_H, R, st)
-        elif lay.cell == IN_CELL:
-            if S.in_ws is None:
-                raise PaigError("interaction_ode_cell: the forward saved no workspace for its backward")
-            names = ["rollout_cell." + n for n in ("rel.0.weight", "rel.0.bias", "rel.2.weight", "rel.2.bias",
-                                                   "obj.0.weight", "obj.0.bias", "obj.2.weight", "obj.2.bias")]
-            with self._p("rollout_in_bwd"):
-                L.paig_rollout_in_bwd(ptr(dpos_roll), ptr(d_pvs), ptr(prm[0]), ptr(prm[2]), ptr(prm[4]), ptr(prm[6]),
-                                      float(lay.H / 2), ptr(dpos0), ptr(dvel0), *[ptr(self.g(n)) for n in names], 0,
-                                      ptr(S.in_ws), S.in_ws.numel() * 4, B, D, lay.in_H, R, st)
-        elif lay.cell in (0, 3):
-            gk, gq = self.g("rollout_cell.k"), self.g("rollout_cell.equil")
-        elif lay.cell == 2:
-            gk = self.g("rollout_cell.g")
-        if lay.cell not in (LSTM_CELL, IN_CELL):
-            L.paig_rollout_bwd(lay.cell, ptr(S.pvs), ptr(dpos_roll), ptr(d_pvs), ptr(prm[0]), ptr(prm[1]), ptr(prm[2]),
-                               ptr(dpos0), ptr(dvel0), ptr(rpart), ptr(gk), ptr(gq), 0, B, D, R, st)
+        if rops.learned and S.roll_ws is None:
+            raise PaigError(f"{self.model.cell_type}: the forward saved no workspace for its backward")
+        with self._p(lay.spec.family.probe_bwd):
+            rops.bwd(ptr(S.pvs), ptr(dpos_roll), ptr(d_pvs), ptr(dpos0), ptr(dvel0),
+                     [ptr(self.g("rollout_cell." + n)) for n in lay.spec.names], ptr(rpart), S.roll_ws, 0, st)
         if S.vel0 is not None and lay.alt_vel:
             self.linear_bwd(S.Xv, dvel0, K * B, "velocity_encoder.init_vel_linear", dXv, None, 0, st, S.ws)
         elif S.vel0 is not None:   # one launch; its partial weight grads join the U-Net's batched slab reduction

@@ -25,6 +25,14 @@ import torch
 import torch.nn as tnn
 
 
+def _forward(self, poss, vels):
+    """One cell step (the physics cells: 5 substeps) on the cell's rollout
+    kernels with R = 1: poss, vels [B, coord_units/2] -> (poss, vels).  The
+    training path runs all R steps in one launch instead (PhysicsNet.forward)."""
+    from paig_reproduction_amd.nn.network import native_modules as _nm
+    return _nm.cell_forward(self, poss, vels)
+
+
 class ode_cell(tnn.RNNCell):
     def __init__(self, input_size, hidden_size):
         super().__init__(input_size, hidden_size)
@@ -40,12 +48,7 @@ class ode_cell(tnn.RNNCell):
         v_0 = torch.zeros(batch_size, self.hidden_size, dtype=dtype)
         return x_0, v_0
 
-    def forward(self, poss, vels):
-        """One cell step (5 substeps) on paig_rollout_fwd/bwd with R = 1:
-        poss, vels [B, coord_units/2] -> (poss, vels).  The training path runs
-        all R steps in one launch instead (PhysicsNet.forward)."""
-        from paig_reproduction_amd.nn.network import native_modules as _nm
-        return _nm.cell_forward(self, poss, vels)
+    forward = _forward
 
 
 class spring_ode_cell(ode_cell):
@@ -109,7 +112,7 @@ class lstm_ode_cell(tnn.Module):
     with lstm = nn.LSTMCell(2D, H) and proj = nn.Linear(H, 2D), D =
     input_size.  Torch's default initialisation; proj is scaled by 0.1, so a
     fresh cell moves objects by about a pixel per step."""
-    KIND = 5   # no kind of paig_rollout_fwd: paig_rollout_lstm_fwd / _bwd
+    KIND = 5   # no kind of the physics kernels: a family of its own (rollout_ops.LSTM)
     H_MAX = 128
 
     def __init__(self, input_size, hidden_size, recurrent_units=100, half=16.0):
@@ -132,11 +135,7 @@ class lstm_ode_cell(tnn.Module):
         return (self.lstm.weight_ih, self.lstm.weight_hh, self.lstm.bias_ih, self.lstm.bias_hh, self.proj.weight,
                 self.proj.bias)
 
-    def forward(self, poss, vels):
-        """One step from a zero hidden state (paig_rollout_lstm_fwd/bwd with
-        R = 1): poss, vels [B, D] -> (poss, vels)."""
-        from paig_reproduction_amd.nn.network import native_modules as _nm
-        return _nm.cell_forward(self, poss, vels)
+    forward = _forward   # (from a zero hidden state)
 
 
 class interaction_ode_cell(tnn.Module):
@@ -153,7 +152,7 @@ class interaction_ode_cell(tnn.Module):
     H), Tanh, Linear(H, 4).  Torch's default initialisation; obj's last layer
     is scaled by 0.1, so a fresh cell moves objects by about a pixel per
     step.  Permutation-equivariant in the objects by construction."""
-    KIND = 6   # no kind of paig_rollout_fwd: paig_rollout_in_fwd / _bwd
+    KIND = 6   # no kind of the physics kernels: a family of its own (rollout_ops.INTERACTION)
     H_MAX = 128
 
     def __init__(self, input_size, hidden_size, recurrent_units=100, half=16.0):
@@ -178,7 +177,4 @@ class interaction_ode_cell(tnn.Module):
         return (self.rel[0].weight, self.rel[0].bias, self.rel[2].weight, self.rel[2].bias, self.obj[0].weight,
                 self.obj[0].bias, self.obj[2].weight, self.obj[2].bias)
 
-    def forward(self, poss, vels):
-        """One step (paig_rollout_in_fwd/bwd with R = 1): poss, vels [B, D] -> (poss, vels)."""
-        from paig_reproduction_amd.nn.network import native_modules as _nm
-        return _nm.cell_forward(self, poss, vels)
+    forward = _forward

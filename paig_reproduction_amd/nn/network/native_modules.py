@@ -4,9 +4,8 @@ nn/network/cells.py, nn/network/stn.py, callable one at a time):
 
   VariableFromNetwork()        blocks.py:318-322   paig_vfn_fwd / paig_vfn_bwd
   VelocityEncoder(inp)         blocks.py:31-49     paig_velmlp_* / paig_vel_pack + paig_gemm_ex
-  <cell>(poss, vels)           cells.py:31-106     paig_rollout_fwd/bwd with R = 1
-  lstm_ode_cell(poss, vels)    (no counterpart)    paig_rollout_lstm_fwd/bwd with R = 1
-  interaction_ode_cell(poss, vels)  (no counterpart)  paig_rollout_in_fwd/bwd with R = 1
+  <cell>(poss, vels)           cells.py:31-106     the cell's rollout kernels (rollout_ops) with R = 1;
+                                                   lstm_ode_cell, interaction_ode_cell: no counterpart
   ShallowUNet / UNet (x)       blocks.py:278-308 / :172-237   the engine's U-Net plan
   ConvolutionalEncoder (inp)   blocks.py:77-103    the engine's encoder stage
   PhysicsNet.conv_st_decoder   physics_models.py:151-199      paig_vfn_* + paig_decoder_*
@@ -27,6 +26,7 @@ import torch
 from paig_reproduction_amd._lib import lib, ptr, stream_handle, require_device
 from paig_reproduction_amd.decoder_ops import DecoderOps, Sigma, Targets
 from paig_reproduction_amd.flat import deposit_grad
+from paig_reproduction_amd.rollout_ops import RolloutOps
 
 
 def _anchor():
@@ -72,158 +72,66 @@ def vfn_forward(mod):
 
 
 # ----------------------------------------------------------- cells --------
-class _Cell(torch.autograd.Function):
+def _obj_rows(v, B, D):
+    """[B][2 n_objs] -> the velocity encoder's row layout [n_objs][B][2] (a relayout copy)."""
+    return v.view(B, D // 2, 2).permute(1, 0, 2).contiguous()
+
+
+def _obj_cols(v, B, D):
+    """[n_objs][B][2] -> [B][2 n_objs]."""
+    return v.view(D // 2, B, 2).permute(1, 0, 2).reshape(B, D)
+
+
+class _RolloutCell(torch.autograd.Function):
+    """<cell>(poss, vels): the cell's rollout kernels with R = 1 (rollout_ops;
+    a learned cell steps from its initial state and saves its activations)."""
+
     @staticmethod
     def forward(ctx, pos, vel, anchor, cell):
         pos, vel = _f32(pos), _f32(vel)
         B, D = pos.shape
         assert vel.shape == (B, D), (tuple(vel.shape), (B, D))
         dev = pos.device
-        kind = cell.KIND
-        p0, p1 = _cell_params(cell)
+        ops = RolloutOps(lib(), cell, B, D, 1, getattr(cell, "half", None))   # (half: the learned cells')
         pvs = torch.empty(B, 2, 2 * D, device=dev)
-        # the kernel takes the initial velocity in the velocity encoder's
-        # row layout [n_objs][B][2] (a relayout copy of [B][2 n_objs])
-        vk = vel.view(B, D // 2, 2).permute(1, 0, 2).contiguous()
-        lib().paig_rollout_fwd(kind, ptr(pos), D, ptr(vk), ptr(cell.dt), ptr(p0), ptr(p1), ptr(pvs), B, D, 1,
-                               stream_handle(dev))
-        ctx.cell, ctx.pvs = cell, pvs
+        vk = _obj_rows(vel, B, D)   # the kernels take the initial velocity in that layout
+        ws = None
+        if ops.learned and (torch.is_grad_enabled() or ctx.needs_input_grad[2]):
+            ws = torch.empty(ops.workspace_floats(), device=dev)
+        ops.fwd(ptr(pos), D, ptr(vk), ptr(pvs), ws, stream_handle(dev))
+        ctx.ops, ctx.pvs, ctx.ws = ops, pvs, ws
         return pvs[:, 1, :D].clone(), pvs[:, 1, D:].clone()
 
     @staticmethod
     def backward(ctx, dpos1, dvel1):
-        cell, pvs = ctx.cell, ctx.pvs
-        B, _, D2 = pvs.shape
-        D = D2 // 2
+        ops, pvs, ws = ctx.ops, ctx.pvs, ctx.ws
+        cell, B, D = ops.cell, ops.B, ops.D
+        if ops.learned and ws is None:
+            raise RuntimeError(f"{type(cell).__name__} step was run without saving activations")
         dev = pvs.device
-        L = lib()
-        dpvs = torch.zeros(B, 2, 2 * D, device=dev)
-        if dpos1 is not None:
-            dpvs[:, 1, :D] = dpos1
-        if dvel1 is not None:
-            dpvs[:, 1, D:] = dvel1
-        dpos_roll = torch.zeros(B, 1, D, device=dev)
-        dpos0, dvel0 = torch.empty(B, D, device=dev), torch.empty(B, D, device=dev)
-        part = torch.empty(2 * L.paig_rollout_bwd_blocks(B), device=dev, dtype=torch.float64)
-        gq = torch.zeros(2, device=dev, dtype=torch.float64)
-        p0, p1 = _cell_params(cell)
-        L.paig_rollout_bwd(cell.KIND, ptr(pvs), ptr(dpos_roll), ptr(dpvs), ptr(cell.dt), ptr(p0), ptr(p1), ptr(dpos0),
-                           ptr(dvel0), ptr(part), ptr(gq), ptr(gq) + 8, 0, B, D, 1, stream_handle(dev))
-        if cell.KIND in (0, 3):
-            deposit_grad(cell.k, gq[0])
-            deposit_grad(cell.equil, gq[1])
-        elif cell.KIND == 2:
-            deposit_grad(cell.g, gq[0])
-        # dvel0 comes back in the [n_objs][B][2] layout
-        return dpos0, dvel0.view(D // 2, B, 2).permute(1, 0, 2).reshape(B, D), None, None
-
-
-def _cell_params(cell):
-    if cell.KIND in (0, 3):   # spring, spring 2-D
-        return cell.k, cell.equil
-    if cell.KIND == 2:
-        return cell.g, cell.m
-    return None, None
-
-
-class _LstmCell(torch.autograd.Function):
-    """lstm_ode_cell(poss, vels): paig_rollout_lstm_fwd / _bwd with R = 1 from a
-    zero hidden state."""
-
-    @staticmethod
-    def forward(ctx, pos, vel, anchor, cell):
-        pos, vel = _f32(pos), _f32(vel)
-        B, D = pos.shape
-        assert vel.shape == (B, D), (tuple(vel.shape), (B, D))
-        dev = pos.device
-        H = cell.recurrent_units
-        L = lib()
-        pvs = torch.empty(B, 2, 2 * D, device=dev)
-        vk = vel.view(B, D // 2, 2).permute(1, 0, 2).contiguous()
-        ws = None
-        if torch.is_grad_enabled() or ctx.needs_input_grad[2]:
-            ws = torch.empty(L.paig_rollout_lstm_workspace(B, D, H, 1) // 4, device=dev)
-        L.paig_rollout_lstm_fwd(ptr(pos), D, ptr(vk), *[ptr(p) for p in cell.weights()], cell.half, ptr(pvs), ptr(ws),
-                                ws.numel() * 4 if ws is not None else 0, B, D, H, 1, stream_handle(dev))
-        ctx.cell, ctx.ws, ctx.shape = cell, ws, (B, D, H)
-        return pvs[:, 1, :D].clone(), pvs[:, 1, D:].clone()
-
-    @staticmethod
-    def backward(ctx, dpos1, dvel1):
-        cell, ws = ctx.cell, ctx.ws
-        B, D, H = ctx.shape
-        if ws is None:
-            raise RuntimeError("lstm_ode_cell step was run without saving activations")
-        dev = ws.device
-        L = lib()
         dpvs = torch.zeros(B, 2, 2 * D, device=dev)
         if dpos1 is not None:
             dpvs[:, 1, :D] = dpos1
         if dvel1 is not None:
             dpvs[:, 1, D:] = dvel1
         dpos0, dvel0 = torch.empty(B, D, device=dev), torch.empty(B, D, device=dev)
-        W = cell.weights()
-        g = [torch.empty_like(p) for p in W]
-        L.paig_rollout_lstm_bwd(None, ptr(dpvs), ptr(W[0]), ptr(W[1]), ptr(W[4]), cell.half, ptr(dpos0), ptr(dvel0),
-                                *[ptr(t) for t in g], 0, ptr(ws), ws.numel() * 4, B, D, H, 1, stream_handle(dev))
-        for p, t in zip(W, g):
+        params = [cell.get_parameter(n) for n in ops.spec.names]
+        if ops.learned:   # one gradient per weight; no adjoint of rolled-out positions (the decoder's) here
+            dpos_roll, g = None, [torch.empty_like(p) for p in params]
+        else:             # (gk, gq): fp64 scalars, whichever of them the cell trains
+            dpos_roll, g = torch.zeros(B, 1, D, device=dev), list(torch.zeros(2, device=dev, dtype=torch.float64))
+        part = torch.empty(ops.part_doubles(), device=dev, dtype=torch.float64)
+        ops.bwd(ptr(pvs), ptr(dpos_roll), ptr(dpvs), ptr(dpos0), ptr(dvel0), [ptr(t) for t in g], ptr(part), ws, 0,
+                stream_handle(dev))
+        for p, t in zip(params, g):
             deposit_grad(p, t)
-        return dpos0, dvel0.view(D // 2, B, 2).permute(1, 0, 2).reshape(B, D), None, None
-
-
-class _InCell(torch.autograd.Function):
-    """interaction_ode_cell(poss, vels): paig_rollout_in_fwd / _bwd with R = 1."""
-
-    @staticmethod
-    def forward(ctx, pos, vel, anchor, cell):
-        pos, vel = _f32(pos), _f32(vel)
-        B, D = pos.shape
-        assert vel.shape == (B, D), (tuple(vel.shape), (B, D))
-        dev = pos.device
-        H = cell.recurrent_units
-        L = lib()
-        pvs = torch.empty(B, 2, 2 * D, device=dev)
-        vk = vel.view(B, D // 2, 2).permute(1, 0, 2).contiguous()
-        ws = None
-        if torch.is_grad_enabled() or ctx.needs_input_grad[2]:
-            ws = torch.empty(L.paig_rollout_in_workspace(B, D, H, 1) // 4, device=dev)
-        L.paig_rollout_in_fwd(ptr(pos), D, ptr(vk), *[ptr(p) for p in cell.weights()], cell.half, ptr(pvs), ptr(ws),
-                              ws.numel() * 4 if ws is not None else 0, B, D, H, 1, stream_handle(dev))
-        ctx.cell, ctx.ws, ctx.shape = cell, ws, (B, D, H)
-        return pvs[:, 1, :D].clone(), pvs[:, 1, D:].clone()
-
-    @staticmethod
-    def backward(ctx, dpos1, dvel1):
-        cell, ws = ctx.cell, ctx.ws
-        B, D, H = ctx.shape
-        if ws is None:
-            raise RuntimeError("interaction_ode_cell step was run without saving activations")
-        dev = ws.device
-        L = lib()
-        dpvs = torch.zeros(B, 2, 2 * D, device=dev)
-        if dpos1 is not None:
-            dpvs[:, 1, :D] = dpos1
-        if dvel1 is not None:
-            dpvs[:, 1, D:] = dvel1
-        dpos0, dvel0 = torch.empty(B, D, device=dev), torch.empty(B, D, device=dev)
-        W = cell.weights()
-        g = [torch.empty_like(p) for p in W]
-        L.paig_rollout_in_bwd(None, ptr(dpvs), ptr(W[0]), ptr(W[2]), ptr(W[4]), ptr(W[6]), cell.half, ptr(dpos0),
-                              ptr(dvel0), *[ptr(t) for t in g], 0, ptr(ws), ws.numel() * 4, B, D, H, 1,
-                              stream_handle(dev))
-        for p, t in zip(W, g):
-            deposit_grad(p, t)
-        return dpos0, dvel0.view(D // 2, B, 2).permute(1, 0, 2).reshape(B, D), None, None
+        return dpos0, _obj_cols(dvel0, B, D), None, None   # (dvel0 comes back in the kernels' layout)
 
 
 def cell_forward(cell, poss, vels):
     """<cell>.forward(poss, vels): 5 substeps (cells.py:31-51 / 60-83 / 96-106),
     or one step of the black-box lstm_ode_cell or of interaction_ode_cell."""
-    if cell.KIND == 5:
-        return _LstmCell.apply(poss, vels, _anchor(), cell)
-    if cell.KIND == 6:
-        return _InCell.apply(poss, vels, _anchor(), cell)
-    return _Cell.apply(poss, vels, _anchor(), cell)
+    return _RolloutCell.apply(poss, vels, _anchor(), cell)
 
 
 # ----------------------------------------------------------- velocity -----

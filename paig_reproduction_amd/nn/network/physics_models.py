@@ -22,6 +22,7 @@ import torch.nn as pnn
 from paig_reproduction_amd._lib import lib, ptr, stream_handle, require_device
 from paig_reproduction_amd.engine import Engine, LossAdjoints, live_steps, materialise
 from paig_reproduction_amd.flat import FlatParams
+from paig_reproduction_amd.rollout_ops import SPECS
 from paig_reproduction_amd.nn.network.base import OPTIMIZERS, BaseNetTorch
 from paig_reproduction_amd.nn.network.blocks import ConvolutionalEncoder, VelocityEncoder, VariableFromNetwork
 from paig_reproduction_amd.nn.network.cells import (bouncing_ode_cell, spring_ode_cell, gravity_ode_cell,
@@ -327,7 +328,7 @@ class PhysicsNet(BaseNetTorch):
         self.encoder = ConvolutionalEncoder(self.conv_input_shape, 200, 2, self.n_objs, self.device)
         self.velocity_encoder = VelocityEncoder(self.alt_vel, self.input_steps, self.n_objs, self.coord_units,
                                                 self.device)
-        if self.cell in (lstm_ode_cell, interaction_ode_cell):
+        if SPECS[self.cell_type].units_ctor:
             self.rollout_cell = self.cell(self.coord_units // 2, self.coord_units // 2, recurrent_units,
                                           self.conv_input_shape[1] / 2)
         else:
@@ -367,17 +368,8 @@ class PhysicsNet(BaseNetTorch):
                  [n for n in names if not n.startswith(self.EARLY_GRADS)])
         if self.learn_sigma:   # the last slot of the fp32 buffer's late part: every other offset as without it
             names.append("decoder_sigma_u")
-        if self.cell_type in ("spring_ode_cell", "spring2d_ode_cell"):
-            names += ["rollout_cell.k", "rollout_cell.equil"]
-        elif self.cell_type == "gravity_ode_cell":
-            names += ["rollout_cell.g"]
-        elif self.cell_type == "lstm_ode_cell":   # fp32: the late part of the fp32 buffer, after every other name
-            names += ["rollout_cell.lstm.weight_ih", "rollout_cell.lstm.weight_hh", "rollout_cell.lstm.bias_ih",
-                      "rollout_cell.lstm.bias_hh", "rollout_cell.proj.weight", "rollout_cell.proj.bias"]
-        elif self.cell_type == "interaction_ode_cell":   # fp32, in the LSTM cell's place
-            names += ["rollout_cell." + n for n in ("rel.0.weight", "rel.0.bias", "rel.2.weight", "rel.2.bias",
-                                                    "obj.0.weight", "obj.0.bias", "obj.2.weight", "obj.2.bias")]
-        return names
+        # the cell's trainable parameters last, in its kernels' gradient order (rollout_ops.SPECS)
+        return names + ["rollout_cell." + n for n in SPECS[self.cell_type].names]
 
     def _init_native(self):
         object.__setattr__(self, "_flat", FlatParams(self, self._live_names(), early=self.EARLY_GRADS))
