@@ -293,8 +293,6 @@ void paig_gemm_splitk_finish(int M, int N, int S, const float* part, float* C, l
                              const float* bias, int act, int auxm, const float* aux, long long ldaux,
                              const float* rowpart, float* rowsum, hipStream_t st);
 
-// MFMA implicit-GEMM convolutions (conv_mfma.hip): return 1 when the shape is
-// instantiated there (launch status in *rc), 0 to fall back to the VALU path.
 // xmax (nullable): per-block max |input| of a split-precision forward
 // (written, n slots) / of the wgrad's X (read: the launch's fixed X scale)
 struct XMax {
@@ -309,17 +307,38 @@ struct XMax {
 // whether no split forward took it (the caller must zero the slots itself).
 void paig_conv_fwd_prezero(float* z, int zn);
 bool paig_conv_fwd_prezero_pending();
-int paig_conv_mfma_fwd(FView in, FViewW out, FView aux, const float* w, const float* b, int F, int Cin, int Cout,
-                       int H, int W, int ks, int flags, hipStream_t st, int* rc, XMax xm, const void* wp = nullptr,
-                       PoolOut pout = PoolOut{nullptr, 0, nullptr, 0});
-int paig_conv_mfma_wgrad(FView x, FView dy, float* slab, int nblk_max, int* nblk_out, int F, int Cin, int Cout, int H,
-                         int W, int ks, int flags, hipStream_t st, int* rc, XMax xm);
+// The operands of a forward / dgrad launch and of a weight-gradient launch
+struct ConvFwdOps {
+  FView in;
+  FViewW out;
+  FView aux;
+  const float* w;
+  const float* b;
+  int F;
+  hipStream_t st;
+  XMax xm;
+  const void* wp;
+  PoolOut pout;
+};
+struct ConvWgOps {
+  FView x, dy;
+  float* slab;
+  int nblk_max;
+  int* nblk_out;
+  int F;
+  hipStream_t st;
+  XMax xm;
+  PoolOut pin;   // the pool fold's pooled gradient and window codes (paig_conv2d_wgrad_pf)
+};
+// One kernel tier's answer for a point (conv.hip states the order of the
+// tiers).  Each looks the point up in its family's resolver; with operands it
+// launches what it found (1: handled, the launch status in *rc; 0: not here,
+// try the next tier), with o == nullptr it only says whether it would (the
+// queries: nothing is launched, *rc untouched).
 // Split-precision 16-bit MFMA convolutions (conv_split.hip), selected by
 // flags & 128 (f16x3 forward / bf16x3 dgrad and wgrad) or flags & 256 (bf16).
-int paig_conv_split_fwd(FView in, FViewW out, FView aux, const float* w, const float* b, int F, int Cin, int Cout,
-                        int H, int W, int ks, int flags, hipStream_t st, int* rc, XMax xm, const void* wp = nullptr,
-                        PoolOut pout = PoolOut{nullptr, 0, nullptr, 0});
-int paig_conv_split_wgrad(FView x, FView dy, float* slab, int nblk_max, int* nblk_out, int F, int Cin, int Cout,
-                          int H, int W, int ks, int flags, hipStream_t st, int* rc, XMax xm,
-                          PoolOut pin = PoolOut{nullptr, 0, nullptr, 0});
-int paig_conv_split_supported(int what, int Cin, int Cout, int H, int W, int ks, int flags);
+int paig_conv_split_fwd(const ConvFwdOps* o, int Cin, int Cout, int H, int W, int ks, int flags, int* rc);
+int paig_conv_split_wgrad(const ConvWgOps* o, int Cin, int Cout, int H, int W, int ks, int flags, int* rc);
+// fp32-input MFMA implicit-GEMM convolutions (conv_mfma.hip)
+int paig_conv_mfma_fwd(const ConvFwdOps* o, int Cin, int Cout, int H, int W, int ks, int flags, int* rc);
+int paig_conv_mfma_wgrad(const ConvWgOps* o, int Cin, int Cout, int H, int W, int ks, int flags, int* rc);

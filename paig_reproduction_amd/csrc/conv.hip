@@ -346,6 +346,33 @@ static int launch_wgrad(FView x, FView dy, float* slab, int nblk_max, int* nblk_
   X(64, 96, 3) X(16, 48, 3) X(32, 128, 3) X(128, 64, 3) X(64, 16, 3) X(8, 3, 3) X(16, 3, 3)    \
   X(8, 3, 1) X(3, 8, 1) X(16, 3, 1) X(3, 16, 1)
 
+// ---- the kernel tiers, in order ---------------------------------------------
+// A convolution runs on the first tier that has its shape: the split-precision
+// MFMA kernels (conv_split.hip; only with flags & 128 or 256), the fp32-input
+// MFMA kernels (conv_mfma.hip), then the direct kernels above.  flags & 16
+// forces the direct kernels.  The fused-upsample input (32), the pool (64) and
+// the transposed-upsample dgrad (512) do not exist on the direct tier, 64 and
+// 512 not on the fp32-input MFMA tier either.  The order is stated here, once
+// for forward / dgrad and once for the weight gradient; launches pass their
+// operands (a tier that launches sets *rc), the queries pass nullptr.
+enum { TIER_NONE = 0, TIER_SPLIT, TIER_MFMA };
+
+static int conv_fwd_upper(const ConvFwdOps* o, int Cin, int Cout, int H, int W, int ks, int flags, int* rc) {
+  if (flags & 16) return TIER_NONE;
+  if ((flags & (128 | 256)) && paig_conv_split_fwd(o, Cin, Cout, H, W, ks, flags, rc)) return TIER_SPLIT;
+  if (flags & (64 | 512)) return TIER_NONE;
+  return paig_conv_mfma_fwd(o, Cin, Cout, H, W, ks, flags, rc) ? TIER_MFMA : TIER_NONE;
+}
+
+// (a weight gradient has no use for 8 and 512 and ignores them; 64 is the
+// split tier's pool fold, reached through paig_conv2d_wgrad_pf, and ignored
+// below it)
+static int conv_wgrad_upper(const ConvWgOps* o, int Cin, int Cout, int H, int W, int ks, int flags, int* rc) {
+  if (flags & 16) return TIER_NONE;
+  if ((flags & (128 | 256)) && paig_conv_split_wgrad(o, Cin, Cout, H, W, ks, flags, rc)) return TIER_SPLIT;
+  return paig_conv_mfma_wgrad(o, Cin, Cout, H, W, ks, flags, rc) ? TIER_MFMA : TIER_NONE;
+}
+
 }  // namespace
 
 extern "C" {
@@ -401,25 +428,18 @@ int paig_conv2d_fwd_pwc(const float* in, long long in_fs, int in_grp, long long 
   const int fl = flags & 7;
   if (F <= 0) return 0;
   int rc = 0;
-  if (flags & 512) {   // dgrad with the transposed-upsample epilogue: split path only
-    if (!(flags & 16) && paig_conv_split_fwd(vin, vout, vaux, w, bias, F, Cin, Cout, H, W, ks, flags, st, &rc,
-                                             XMax{xmax, xmax_n}, wprep, PoolOut{pool_out, pool_fs, pool_code,
-                                                                                 pool_code_fs}))
-      return rc;
-    paig_set_error("paig_conv2d_fwd: no transposed-upsample dgrad (flags & 512) for Cin=%d Cout=%d H=%d flags=%d", Cin,
-                   Cout, H, flags);
-    return PAIG_E_UNSUPPORTED;
-  }
-  if ((flags & 64) && (flags & 16)) {
-    paig_set_error("paig_conv2d_fwd: the fused pool (flags & 64) needs the split path");
-    return PAIG_E_UNSUPPORTED;
-  }
-  if (!(flags & 16) &&
-      paig_conv_mfma_fwd(vin, vout, vaux, w, bias, F, Cin, Cout, H, W, ks, flags, st, &rc, XMax{xmax, xmax_n}, wprep,
-                         PoolOut{pool_out, pool_fs, pool_code, pool_code_fs}))
-    return rc;
-  if (flags & 32) {
-    paig_set_error("paig_conv2d_fwd: fused-upsample input has no instantiation for Cin=%d Cout=%d H=%d", Cin, Cout, H);
+  const ConvFwdOps ops{vin, vout, vaux, w, bias, F, st, XMax{xmax, xmax_n}, wprep,
+                       PoolOut{pool_out, pool_fs, pool_code, pool_code_fs}};
+  if (conv_fwd_upper(&ops, Cin, Cout, H, W, ks, flags, &rc)) return rc;
+  if (flags & (32 | 64 | 512)) {   // not on the direct tier
+    if (flags & 512)
+      paig_set_error("paig_conv2d_fwd: no transposed-upsample dgrad (flags & 512) for Cin=%d Cout=%d H=%d flags=%d",
+                     Cin, Cout, H, flags);
+    else if (flags & 64)
+      paig_set_error("paig_conv2d_fwd: the fused pool (flags & 64) needs a split-path shape");
+    else
+      paig_set_error("paig_conv2d_fwd: fused-upsample input has no instantiation for Cin=%d Cout=%d H=%d", Cin, Cout,
+                     H);
     return PAIG_E_UNSUPPORTED;
   }
 #define PAIG_CASE(CI, CO, K)                                                                   \
@@ -455,9 +475,9 @@ int paig_conv2d_wgrad_ex(const float* x, long long x_fs, int x_grp, long long x_
   *nblk_out = 0;
   if (F <= 0) return 0;
   int rc = 0;
-  if (!(flags & 16) && paig_conv_mfma_wgrad(vx, vd, slab, nblk_max, nblk_out, F, Cin, Cout, H, W, ks, flags, st, &rc,
-                                             XMax{const_cast<float*>(xmax), xmax_n}))
-    return rc;
+  const ConvWgOps ops{vx, vd, slab, nblk_max, nblk_out, F, st, XMax{const_cast<float*>(xmax), xmax_n},
+                      PoolOut{nullptr, 0, nullptr, 0}};
+  if (conv_wgrad_upper(&ops, Cin, Cout, H, W, ks, flags, &rc)) return rc;
   if (flags & 32) {
     paig_set_error("paig_conv2d_wgrad: fused-upsample input has no instantiation for Cin=%d Cout=%d H=%d", Cin, Cout, H);
     return PAIG_E_UNSUPPORTED;
@@ -479,12 +499,42 @@ int paig_conv2d_wgrad_pf(const float* x, long long x_fs, int x_grp, long long x_
   PAIG_REQUIRE((flags & 64) && (flags & 128) && dpool && pcode,
                "paig_conv2d_wgrad_pf: needs flags 64 | 128, the pooled gradient and the window codes");
   int rc = 0;
-  if (paig_conv_split_wgrad(FView{x, x_fs, x_gs, x_grp}, FView{dy, dy_fs, 0, 0}, slab, nblk_max, nblk_out, F, Cin, Cout,
-                            H, W, ks, flags, (hipStream_t)stream, &rc, XMax{const_cast<float*>(xmax), xmax_n},
-                            PoolOut{const_cast<float*>(dpool), dpool_fs, const_cast<unsigned char*>(pcode), pcode_fs}))
-    return rc;
+  const ConvWgOps ops{FView{x, x_fs, x_gs, x_grp}, FView{dy, dy_fs, 0, 0}, slab, nblk_max, nblk_out, F,
+                      (hipStream_t)stream, XMax{const_cast<float*>(xmax), xmax_n},
+                      PoolOut{const_cast<float*>(dpool), dpool_fs, const_cast<unsigned char*>(pcode), pcode_fs}};
+  if (paig_conv_split_wgrad(&ops, Cin, Cout, H, W, ks, flags, &rc)) return rc;   // the fold is the split tier's alone
   paig_set_error("paig_conv2d_wgrad_pf: no pool-fold instantiation for Cin=%d Cout=%d H=%d", Cin, Cout, H);
   return PAIG_E_UNSUPPORTED;
+}
+
+// Query (see include/paig_hip.h): does paig_conv2d_fwd (what = 0) or
+// paig_conv2d_wgrad (what = 1) run this shape on an MFMA tier with these
+// flags?  Flags 32, 64 and 512 exist ONLY there, so the host uses this to
+// decide which upsamples and pools it may fuse (csrc/unet.hip).  The answer
+// is the tier statement's above (flags & 16, the A/B switch past the tiers,
+// is not part of the question).
+int paig_conv2d_mfma_supported(int what, int Cin, int Cout, int H, int W, int ks, int flags) {
+  flags &= ~16;
+  const bool dg = (flags & 8) != 0;
+  if (what == 0) {
+    if (conv_fwd_upper(nullptr, Cin, Cout, H, W, ks, flags, nullptr)) return 1;
+    // Kept answers: flags & 512 has one form (8 | 128 | 512, answered above).
+    // In any other combination no launch takes it, but this query has always
+    // answered such a point as if the bit were clear -- for a pooled forward
+    // and on the fp32-input MFMA tier.  No caller asks; the recorded answers
+    // (tests/test_conv_routing.py) hold them until the interface drops them.
+    if (!(flags & 512)) return 0;
+    if (flags & 64) return !dg && paig_conv_split_fwd(nullptr, Cin, Cout, H, W, ks, flags & ~512, nullptr);
+    return paig_conv_mfma_fwd(nullptr, Cin, Cout, H, W, ks, flags & ~512, nullptr);
+  }
+  // Kept answers, likewise: a weight gradient ignores 8 and 512 (and 64 below
+  // the split tier), while this query has always refused 8 with 32, the split
+  // tier with 512, and 64 below the split tier.
+  if (dg && (flags & 32)) return 0;
+  int tier = conv_wgrad_upper(nullptr, Cin, Cout, H, W, ks, flags, nullptr);
+  if (tier == TIER_SPLIT && (flags & 512))
+    tier = paig_conv_mfma_wgrad(nullptr, Cin, Cout, H, W, ks, flags, nullptr) ? TIER_MFMA : TIER_NONE;
+  return tier == TIER_SPLIT || (tier == TIER_MFMA && !(flags & 64));
 }
 
 }  // extern "C"

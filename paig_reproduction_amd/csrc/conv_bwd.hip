@@ -1446,27 +1446,49 @@ static int sbwd_launch(FView x, FView dy, FViewW dx, FView aux, const float* w, 
   X(8, 8, 36) X(8, 16, 18) X(16, 16, 18) X(32, 16, 18) X(24, 8, 36)                            \
   X(16, 16, 64) X(16, 32, 32)
 
+// ---- routing: the one place a fused layer is looked up -----------------------
+// A route is the sbwd_launch instantiation of a point.  sbwd_resolve applies
+// the flag rules and walks the shape lists above, each once; the query
+// (paig_conv2d_bwd_supported) is "it found one" and the launch
+// (paig_conv2d_bwd) calls what it found, so a shape is added to one list and
+// nowhere else.
+using SBwdFn = int (*)(FView x, FView dy, FViewW dx, FView aux, const float* w, int flags, float* slab, int nblk_max,
+                       int* nblk_out, int F, hipStream_t st, XMax xm, const void* wp, FView dpool,
+                       const unsigned char* pcode, long long pcode_fs);
+
+template <bool UPS, bool PF>
+static SBwdFn sbwd_pick(int Cin, int Cout, int H, bool b16) {
+#define PAIG_CASE(CI, CO, HH)                                               \
+  if (Cin == CI && Cout == CO && H == HH)                                   \
+    return b16 ? &sbwd_launch<CI, CO, HH, HH, 3, UPS, 2, PF> : &sbwd_launch<CI, CO, HH, HH, 3, UPS, 0, PF>;
+  if constexpr (PF) {
+    PAIG_BWD_POOL_SHAPES(PAIG_CASE)
+  } else if constexpr (UPS) {
+    PAIG_BWD_UP_SHAPES(PAIG_CASE)
+  } else {
+    PAIG_BWD_SHAPES(PAIG_CASE)
+  }
+#undef PAIG_CASE
+  return nullptr;
+}
+
+// flags: 128 / 256 the arithmetic (one is needed), 64 the pool fold, 32 the
+// fused-upsample input (not both), 1024 rows in accumulator order (only where
+// the shape's kernel writes them: sbwd_fragrows)
+static SBwdFn sbwd_resolve(int Cin, int Cout, int H, int W, int ks, int flags) {
+  if (H != W || ks != 3 || !(flags & (128 | 256))) return nullptr;
+  const bool b16 = (flags & 256) != 0, pool = (flags & 64) != 0, up = (flags & 32) != 0;
+  if ((flags & 1024) && !sbwd_fragrows(Cin, Cout, H, b16 ? 2 : 0, pool)) return nullptr;
+  if (pool) return up ? nullptr : sbwd_pick<false, true>(Cin, Cout, H, b16);
+  return up ? sbwd_pick<true, false>(Cin, Cout, H, b16) : sbwd_pick<false, false>(Cin, Cout, H, b16);
+}
+
 }  // namespace
 
 extern "C" {
 
 int paig_conv2d_bwd_supported(int Cin, int Cout, int H, int W, int ks, int flags) {
-  if (H != W || ks != 3 || !(flags & (128 | 256))) return 0;
-  if ((flags & 1024) && !sbwd_fragrows(Cin, Cout, H, flags & 256 ? 2 : 0, (flags & 64) != 0)) return 0;
-#define PAIG_CASE(CI, CO, HH) \
-  if (Cin == CI && Cout == CO && H == HH) return 1;
-  if (flags & 64) {
-    if (flags & 32) return 0;
-    PAIG_BWD_POOL_SHAPES(PAIG_CASE)
-    return 0;
-  }
-  if (flags & 32) {
-    PAIG_BWD_UP_SHAPES(PAIG_CASE)
-    return 0;
-  }
-  PAIG_BWD_SHAPES(PAIG_CASE)
-#undef PAIG_CASE
-  return 0;
+  return sbwd_resolve(Cin, Cout, H, W, ks, flags) != nullptr;
 }
 
 size_t paig_conv2d_bwd_slab_len(int Cin, int Cout, int ks, int flags) {
@@ -1481,51 +1503,18 @@ int paig_conv2d_bwd(const float* x, long long x_fs, int x_grp, long long x_gs, c
                     const unsigned char* pcode, long long pcode_fs, const void* wprep, void* stream) {
   *nblk_out = 0;
   if (F <= 0) return 0;
-  PAIG_REQUIRE(paig_conv2d_bwd_supported(Cin, Cout, H, W, ks, flags),
-               "paig_conv2d_bwd: no fused kernel for Cin=%d Cout=%d H=%d W=%d ks=%d flags=%d", Cin, Cout, H, W, ks,
-               flags);
+  const SBwdFn launch = sbwd_resolve(Cin, Cout, H, W, ks, flags);
+  PAIG_REQUIRE(launch, "paig_conv2d_bwd: no fused kernel for Cin=%d Cout=%d H=%d W=%d ks=%d flags=%d", Cin, Cout, H, W,
+               ks, flags);
   PAIG_REQUIRE(x_grp == 0 || H * W >= 256, "paig_conv2d_bwd: multi-frame tiles need a plain frame stride");
   PAIG_REQUIRE(nblk_max > 0 && slab && dx && dy && x && w, "paig_conv2d_bwd: null operand or no slab rows");
-  hipStream_t st = (hipStream_t)stream;
-  FView vx{x, x_fs, x_gs, x_grp}, vd{dy, dy_fs, 0, 0}, va{aux, aux_fs, 0, 0};
-  FViewW vdx{dx, dx_fs};
-  XMax xm{const_cast<float*>(xmax), xmax_n};
-  const bool b16 = (flags & 256) != 0;
-  const int fl = flags & (6 | 1024);
   PAIG_REQUIRE(!(flags & 1024) || (reinterpret_cast<uintptr_t>(slab) & 15) == 0,
                "paig_conv2d_bwd: rows in accumulator order (flags & 1024) need a 16-byte aligned slab");
-  if (flags & 64) {
-    const FView vp{dpool, dpool_fs, 0, 0};
-#define PAIG_CASE(CI, CO, HH)                                                                                     \
-  if (Cin == CI && Cout == CO && H == HH)                                                                         \
-    return b16 ? sbwd_launch<CI, CO, HH, HH, 3, false, 2, true>(vx, vd, vdx, va, w, fl, slab, nblk_max, nblk_out,  \
-                                                                 F, st, xm, wprep, vp, pcode, pcode_fs)            \
-               : sbwd_launch<CI, CO, HH, HH, 3, false, 0, true>(vx, vd, vdx, va, w, fl, slab, nblk_max, nblk_out,  \
-                                                                 F, st, xm, wprep, vp, pcode, pcode_fs);
-    PAIG_BWD_POOL_SHAPES(PAIG_CASE)
-#undef PAIG_CASE
-    return PAIG_E_UNSUPPORTED;
-  }
-  if (flags & 32) {
-#define PAIG_CASE(CI, CO, HH)                                                                                     \
-  if (Cin == CI && Cout == CO && H == HH)                                                                         \
-    return b16 ? sbwd_launch<CI, CO, HH, HH, 3, true, 2>(vx, vd, vdx, va, w, fl, slab, nblk_max, nblk_out, F, st, \
-                                                           xm, wprep)                                             \
-               : sbwd_launch<CI, CO, HH, HH, 3, true, 0>(vx, vd, vdx, va, w, fl, slab, nblk_max, nblk_out, F, st, \
-                                                           xm, wprep);
-    PAIG_BWD_UP_SHAPES(PAIG_CASE)
-#undef PAIG_CASE
-    return PAIG_E_UNSUPPORTED;
-  }
-#define PAIG_CASE(CI, CO, HH)                                                                                      \
-  if (Cin == CI && Cout == CO && H == HH)                                                                          \
-    return b16 ? sbwd_launch<CI, CO, HH, HH, 3, false, 2>(vx, vd, vdx, va, w, fl, slab, nblk_max, nblk_out, F, st, \
-                                                            xm, wprep)                                             \
-               : sbwd_launch<CI, CO, HH, HH, 3, false, 0>(vx, vd, vdx, va, w, fl, slab, nblk_max, nblk_out, F, st, \
-                                                            xm, wprep);
-  PAIG_BWD_SHAPES(PAIG_CASE)
-#undef PAIG_CASE
-  return PAIG_E_UNSUPPORTED;
+  const bool pf = (flags & 64) != 0;   // the pool operands go to the pool-fold kernels only
+  return launch(FView{x, x_fs, x_gs, x_grp}, FView{dy, dy_fs, 0, 0}, FViewW{dx, dx_fs}, FView{aux, aux_fs, 0, 0}, w,
+                flags & (6 | 1024), slab, nblk_max, nblk_out, F, (hipStream_t)stream,
+                XMax{const_cast<float*>(xmax), xmax_n}, wprep, FView{pf ? dpool : nullptr, pf ? dpool_fs : 0, 0, 0},
+                pf ? pcode : nullptr, pf ? pcode_fs : 0);
 }
 
 #ifdef PAIG_BWD_STAMPS

@@ -18,6 +18,7 @@
 //   cross-wave reduction, one partial row per block (paig_slab_reduce*).
 // LDS layouts are padded so every fragment read is bank-conflict free
 // (lanes 0-15 and 16-31 of a ds_read_b32 group land on disjoint halves).
+#include "conv_shapes.h"
 #include "conv_tile.h"
 
 namespace {
@@ -664,119 +665,74 @@ static int wgrad_launch(FView x, FView dy, float* slab, int nblk_max, int* nblk_
   return 0;
 }
 
-// (CIN, COUT, H, KS): ShallowUNet(hidden 8) at 32x32 -- forward and dgrad
-// shapes (dgrad kernel shapes are (layer Cout, layer Cin)); *_UP: convs whose
-// input is the fused 2x upsample (c7, c10).
-#define PAIG_MFMA_FWD(X)                                                                                  \
-  X(3, 8, 32, 3) X(8, 8, 32, 3) X(8, 16, 16, 3) X(16, 16, 16, 3) X(16, 32, 8, 3) X(32, 32, 8, 3)         \
-  X(32, 16, 16, 3) X(16, 16, 32, 3) X(24, 8, 32, 3) X(8, 2, 32, 1) X(16, 8, 16, 3) X(8, 24, 32, 3)       \
-  X(2, 8, 32, 1) X(32, 16, 8, 3) X(16, 32, 16, 3)
-#define PAIG_MFMA_WG(X)                                                                                   \
-  X(3, 8, 32, 3) X(8, 8, 32, 3) X(8, 16, 16, 3) X(16, 16, 16, 3) X(16, 32, 8, 3) X(32, 32, 8, 3)         \
-  X(32, 16, 16, 3) X(16, 16, 32, 3) X(24, 8, 32, 3) X(8, 2, 32, 1)
-#define PAIG_MFMA_UP(X) X(32, 16, 16, 3) X(16, 16, 32, 3)
 // (CIN, H) of the Cout = 8, 3x3 shapes on the pixel-pair kernel (fwd: c1, c2,
-// c11, c12; dgrad: c2/c12 (8 -> 8 at 32) and c3 (16 -> 8 at 16))
+// c11, c12; dgrad: c2/c12 (8 -> 8 at 32) and c3 (16 -> 8 at 16)); the other
+// lists of this tier are the ShallowUNet 32 x 32 shapes of conv_shapes.h
 #define PAIG_MFMA_PAIR(X) X(3, 32) X(8, 32) X(24, 32) X(16, 16)
 
-}  // namespace
+// ---- routing: the one place a shape of this tier is looked up ----------------
+// A route is the launcher instantiation of a point.  The resolvers apply the
+// tier's flag rules (8 dgrad, 32 input = 2x upsample of (H/2 x W/2)) and walk
+// each list once; launch and query both go through them (paig_conv_mfma_fwd /
+// _wgrad below), so a shape is added to one list and nowhere else.
+using MFwdFn = int (*)(FView in, FViewW out, FView aux, const float* w, const float* b, int F, int flags,
+                       hipStream_t st);
+using MWgFn = int (*)(FView x, FView dy, float* slab, int nblk_max, int* nblk_out, int F, hipStream_t st);
 
-// Returns 1 if handled (rc in *rc), 0 if the shape has no MFMA instantiation.
-// flags: 1 relu, 2 mask(aux>0), 4 accumulate, 8 dgrad, 32 input = 2x upsample of (H/2 x W/2)
-int paig_conv_mfma_fwd(FView in, FViewW out, FView aux, const float* w, const float* b, int F, int Cin, int Cout,
-                       int H, int W, int ks, int flags, hipStream_t st, int* rc, XMax xm, const void* wp,
-                       PoolOut pout) {
-  if ((flags & (128 | 256)) &&
-      paig_conv_split_fwd(in, out, aux, w, b, F, Cin, Cout, H, W, ks, flags, st, rc, xm, wp, pout))
-    return 1;
-  if (flags & 64) {
-    paig_set_error("paig_conv2d_fwd: the fused pool (flags & 64) needs a split-path shape");
-    *rc = PAIG_E_UNSUPPORTED;
-    return 1;
-  }
+static MFwdFn mfwd_resolve(int Cin, int Cout, int H, int W, int ks, int flags) {
   const bool dg = (flags & 8) != 0;
-  const bool up = (flags & 32) != 0;
-  const int fl = flags & 7;
-  if (H != W) return 0;
-  if (up) {
-    if (dg) return 0;
-#define PAIG_CASE(CI, CO, HH, K)                                                              \
-    if (Cin == CI && Cout == CO && H == HH && ks == K) {                                      \
-      *rc = fwd_launch<CI, CO, HH, HH, K, false, true>(in, out, aux, w, b, F, fl, st);        \
-      return 1;                                                                               \
-    }
-    PAIG_MFMA_UP(PAIG_CASE)
+  if (H != W) return nullptr;
+  if (flags & 32) {
+    if (dg) return nullptr;
+#define PAIG_CASE(CI, CO, HH, K) \
+    if (Cin == CI && Cout == CO && H == HH && ks == K) return &fwd_launch<CI, CO, HH, HH, K, false, true>;
+    PAIG_SUNET32_UP(PAIG_CASE)
 #undef PAIG_CASE
-    return 0;
+    return nullptr;
   }
-  if (Cout == 8 && ks == 3 && !(flags & 64)) {
-#define PAIG_PCASE(CI, HH)                                                                   \
-    if (Cin == CI && H == HH) {                                                              \
-      *rc = dg ? pair_launch<CI, HH, HH, true>(in, out, aux, w, b, F, fl, st)                \
-               : pair_launch<CI, HH, HH, false>(in, out, aux, w, b, F, fl, st);              \
-      return 1;                                                                              \
-    }
+  if (Cout == 8 && ks == 3) {
+#define PAIG_PCASE(CI, HH) \
+    if (Cin == CI && H == HH) return dg ? &pair_launch<CI, HH, HH, true> : &pair_launch<CI, HH, HH, false>;
     PAIG_MFMA_PAIR(PAIG_PCASE)
 #undef PAIG_PCASE
   }
-#define PAIG_CASE(CI, CO, HH, K)                                                                      \
-  if (Cin == CI && Cout == CO && H == HH && ks == K) {                                                \
-    *rc = dg ? fwd_launch<CI, CO, HH, HH, K, true, false>(in, out, aux, w, b, F, fl, st)              \
-             : fwd_launch<CI, CO, HH, HH, K, false, false>(in, out, aux, w, b, F, fl, st);            \
-    return 1;                                                                                         \
-  }
-  PAIG_MFMA_FWD(PAIG_CASE)
+#define PAIG_CASE(CI, CO, HH, K)                      \
+  if (Cin == CI && Cout == CO && H == HH && ks == K) \
+    return dg ? &fwd_launch<CI, CO, HH, HH, K, true, false> : &fwd_launch<CI, CO, HH, HH, K, false, false>;
+  PAIG_SUNET32_FWD(PAIG_CASE)
 #undef PAIG_CASE
-  return 0;
+  return nullptr;
 }
 
-int paig_conv_mfma_wgrad(FView x, FView dy, float* slab, int nblk_max, int* nblk_out, int F, int Cin, int Cout, int H,
-                         int W, int ks, int flags, hipStream_t st, int* rc, XMax xm) {
-  if ((flags & (128 | 256)) &&
-      paig_conv_split_wgrad(x, dy, slab, nblk_max, nblk_out, F, Cin, Cout, H, W, ks, flags, st, rc, xm))
-    return 1;
-  if (H != W) return 0;
+static MWgFn mwg_resolve(int Cin, int Cout, int H, int W, int ks, int flags) {
+  if (H != W) return nullptr;
   if (flags & 32) {
-#define PAIG_CASE(CI, CO, HH, K)                                                                 \
-    if (Cin == CI && Cout == CO && H == HH && ks == K) {                                         \
-      *rc = wgrad_launch<CI, CO, HH, HH, K, true>(x, dy, slab, nblk_max, nblk_out, F, st);       \
-      return 1;                                                                                  \
-    }
-    PAIG_MFMA_UP(PAIG_CASE)
+#define PAIG_CASE(CI, CO, HH, K) \
+    if (Cin == CI && Cout == CO && H == HH && ks == K) return &wgrad_launch<CI, CO, HH, HH, K, true>;
+    PAIG_SUNET32_UP(PAIG_CASE)
 #undef PAIG_CASE
-    return 0;
+    return nullptr;
   }
-#define PAIG_CASE(CI, CO, HH, K)                                                         \
-  if (Cin == CI && Cout == CO && H == HH && ks == K) {                                   \
-    *rc = wgrad_launch<CI, CO, HH, HH, K, false>(x, dy, slab, nblk_max, nblk_out, F, st); \
-    return 1;                                                                            \
-  }
-  PAIG_MFMA_WG(PAIG_CASE)
+#define PAIG_CASE(CI, CO, HH, K) \
+  if (Cin == CI && Cout == CO && H == HH && ks == K) return &wgrad_launch<CI, CO, HH, HH, K, false>;
+  PAIG_SUNET32_WG(PAIG_CASE)
 #undef PAIG_CASE
-  return 0;
+  return nullptr;
 }
 
-// Query (see include/paig_hip.h): does paig_conv2d_fwd (what = 0) or
-// paig_conv2d_wgrad (what = 1) run this shape on the MFMA path with these
-// flags?  flags & 32 (fused 2x upsample input) exists ONLY on that path, so
-// the host uses this to decide which upsamples it may fuse.
-extern "C" int paig_conv2d_mfma_supported(int what, int Cin, int Cout, int H, int W, int ks, int flags) {
-  if ((flags & (128 | 256)) && paig_conv_split_supported(what, Cin, Cout, H, W, ks, flags)) return 1;
-  if (flags & 64) return 0;   // the fused pool exists on the split path only
-  if (H != W) return 0;
-  const bool up = (flags & 32) != 0, dg = (flags & 8) != 0;
-#define PAIG_CASE(CI, CO, HH, K) \
-  if (Cin == CI && Cout == CO && H == HH && ks == K) return 1;
-  if (up) {
-    if (dg) return 0;
-    PAIG_MFMA_UP(PAIG_CASE)
-    return 0;
-  }
-  if (what == 0) {
-    PAIG_MFMA_FWD(PAIG_CASE)
-  } else {
-    PAIG_MFMA_WG(PAIG_CASE)
-  }
-#undef PAIG_CASE
-  return 0;
+}  // namespace
+
+// flags: 1 relu, 2 mask(aux>0), 4 accumulate, 8 dgrad, 32 fused-upsample input
+int paig_conv_mfma_fwd(const ConvFwdOps* o, int Cin, int Cout, int H, int W, int ks, int flags, int* rc) {
+  const MFwdFn launch = mfwd_resolve(Cin, Cout, H, W, ks, flags);
+  if (!o || !launch) return launch != nullptr;
+  *rc = launch(o->in, o->out, o->aux, o->w, o->b, o->F, flags & 7, o->st);
+  return 1;
+}
+
+int paig_conv_mfma_wgrad(const ConvWgOps* o, int Cin, int Cout, int H, int W, int ks, int flags, int* rc) {
+  const MWgFn launch = mwg_resolve(Cin, Cout, H, W, ks, flags);
+  if (!o || !launch) return launch != nullptr;
+  *rc = launch(o->x, o->dy, o->slab, o->nblk_max, o->nblk_out, o->F, o->st);
+  return 1;
 }

@@ -38,6 +38,7 @@
 //   absorbs the tap shift (any pixel offset, no misaligned vector reads); the
 //   16 columns of an N-tile are 4 (tap, 4-channel) quads.  Bias gradients
 //   are summed exactly in fp32 from the staging registers.
+#include "conv_shapes.h"
 #include "split_common.h"
 
 #ifndef PAIG_FWD_AUXP
@@ -2044,21 +2045,14 @@ static int swg_launch(FView x, FView dy, float* slab, int nblk_max, int* nblk_ou
   return 0;
 }
 
-// (CIN, COUT, H, KS) of the ShallowUNet(hidden 8) shapes at 32x32: forward
-// and dgrad kernel shapes (dgrad shapes are (layer Cout, layer Cin)); *_UP:
-// the convs whose input is the fused 2x upsample (c7, c10)
-#define PAIG_SPLIT_FWD(X)                                                                                 \
-  X(3, 8, 32, 3) X(8, 8, 32, 3) X(8, 16, 16, 3) X(16, 16, 16, 3) X(16, 32, 8, 3) X(32, 32, 8, 3)         \
-  X(32, 16, 16, 3) X(16, 16, 32, 3) X(24, 8, 32, 3) X(8, 2, 32, 1) X(16, 8, 16, 3) X(8, 24, 32, 3)       \
-  X(2, 8, 32, 1) X(32, 16, 8, 3) X(16, 32, 16, 3)                                                         \
-  PAIG_SPLIT_FWD_3BP(X) PAIG_SPLIT_FWD_UNET(X)
-#define PAIG_SPLIT_WG(X)                                                                                  \
-  X(3, 8, 32, 3) X(8, 8, 32, 3) X(8, 16, 16, 3) X(16, 16, 16, 3) X(16, 32, 8, 3) X(32, 32, 8, 3)         \
-  X(32, 16, 16, 3) X(16, 16, 32, 3) X(24, 8, 32, 3) X(8, 2, 32, 1)                                        \
-  PAIG_SPLIT_WG_3BP(X) PAIG_SPLIT_WG_UNET(X)
-#define PAIG_SPLIT_UP(X)                                                                                  \
-  X(32, 16, 16, 3) X(16, 16, 32, 3) X(32, 16, 18, 3) X(16, 16, 36, 3) X(128, 32, 16, 3) X(64, 32, 32, 3) \
-  X(32, 32, 64, 3)
+// (CIN, COUT, H, KS): the ShallowUNet(hidden 8) shapes at 32x32
+// (conv_shapes.h, shared with conv_mfma.hip), then 3bp's and the UNet's.
+// Forward and dgrad kernel shapes (dgrad shapes are (layer Cout, layer Cin));
+// *_UP: the convs whose input is the fused 2x upsample (c7, c10)
+#define PAIG_SPLIT_FWD(X) PAIG_SUNET32_FWD(X) PAIG_SPLIT_FWD_3BP(X) PAIG_SPLIT_FWD_UNET(X)
+#define PAIG_SPLIT_WG(X) PAIG_SUNET32_WG(X) PAIG_SPLIT_WG_3BP(X) PAIG_SPLIT_WG_UNET(X)
+#define PAIG_SPLIT_UP(X) \
+  PAIG_SUNET32_UP(X) X(32, 16, 18, 3) X(16, 16, 36, 3) X(128, 32, 16, 3) X(64, 32, 32, 3) X(32, 32, 64, 3)
 // UNet convs whose output's max pool is folded into their separate weight
 // gradient's dY staging and their data gradient's input staging (flags & 64;
 // c4: too wide for the fused layer backward): (Cin, Cout) of the layer.  c6
@@ -2096,147 +2090,115 @@ static int swg_launch(FView x, FView dy, float* slab, int nblk_max, int* nblk_ou
   X(3, 8, 36, 3) X(8, 8, 36, 3) X(8, 16, 18, 3) X(16, 16, 18, 3) X(16, 32, 9, 3) X(32, 32, 9, 3)         \
   X(32, 16, 18, 3) X(16, 16, 36, 3) X(24, 8, 36, 3) X(8, 3, 36, 1)
 
-}  // namespace
+// ---- routing: the one place a shape of this tier is looked up ----------------
+// A route is the launcher instantiation of a point and what its branch
+// forwards.  The resolvers apply the tier's flag rules (128 split precision:
+// f16 x3 forward and scaled dgrad, bf16 x3 wgrad; 256 bf16 hi only; 8 dgrad;
+// 32 fused-upsample input; 64 the max pool of the output: fused into the
+// forward, its backward folded into the dgrad's and the wgrad's staging; 512
+// dgrad writing the transposed upsample of dX) and walk each list once.
+// Launch and query both go through them (paig_conv_split_fwd / _wgrad
+// below), so a shape is added to one list and nowhere else.
+using SFwdFn = int (*)(FView in, FViewW out, FView aux, const float* w, const float* b, int F, int flags,
+                       hipStream_t st, XMax xm, const void* wp, PoolOut pout);
+using SWgFn = int (*)(FView x, FView dy, float* slab, int nblk_max, int* nblk_out, int F, hipStream_t st, XMax xm,
+                      PoolOut pin);
+struct SFwdRoute {
+  SFwdFn launch = nullptr;
+  int mask = 0;          // the flags the launcher takes
+  bool nopool = false;   // flags & 64 on a forward whose tiling cannot pool (!POOLOK): the launcher refuses
+};
 
-// flags & 128: split precision (f16 x3 forward and scaled dgrad), flags & 256:
-// bf16 hi only.  Returns 1 if the shape is instantiated here (rc in *rc).
-int paig_conv_split_fwd(FView in, FViewW out, FView aux, const float* w, const float* b, int F, int Cin, int Cout,
-                        int H, int W, int ks, int flags, hipStream_t st, int* rc, XMax xm, const void* wp,
-                        PoolOut pout) {
-  const bool dg = (flags & 8) != 0, up = (flags & 32) != 0, b16 = (flags & 256) != 0;
-  const int fl = flags & (7 | 64);
-  if (H != W || !(flags & (128 | 256))) return 0;
-  if (in.grp > 0 && H * W < 256) return 0;   // multi-frame tiles step frames by a plain stride
-  if (dg && (flags & 64)) {   // dgrad with the output max pool's backward folded into its input staging (PF)
-    if (up || b16 || (flags & 512)) return 0;
-#define PAIG_CASE(CI, CO, HH, K)                                                                          \
-    if (Cin == CO && Cout == CI && H == HH && ks == K) {                                                  \
-      *rc = sfwd_launch<CO, CI, HH, HH, K, true, false, 0, false, true>(in, out, aux, w, b, F, fl & 7, st, xm, wp, pout); \
-      return 1;                                                                                           \
-    }
+static SFwdRoute sfwd_resolve(int Cin, int Cout, int H, int W, int ks, int flags) {
+  const bool dg = (flags & 8) != 0, up = (flags & 32) != 0, b16 = (flags & 256) != 0, pool = (flags & 64) != 0;
+  if (H != W || !(flags & (128 | 256))) return {};
+  if (dg && pool) {   // dgrad with the output max pool's backward folded into its input staging (PF)
+    if (up || b16 || (flags & 512)) return {};
+#define PAIG_CASE(CI, CO, HH, K)                      \
+    if (Cin == CO && Cout == CI && H == HH && ks == K) \
+      return {&sfwd_launch<CO, CI, HH, HH, K, true, false, 0, false, true>, 7};
     PAIG_SPLIT_PF(PAIG_CASE)
 #undef PAIG_CASE
-    return 0;
+    return {};
   }
   if (flags & 512) {   // dgrad writing the transposed upsample of dX (UPT)
-    if (!dg || up || b16 || (flags & (4 | 64))) return 0;
-#define PAIG_CASE(CI, CO, HH, K)                                                                          \
-    if (Cin == CI && Cout == CO && H == HH && ks == K) {                                                  \
-      *rc = sfwd_launch<CI, CO, HH, HH, K, true, false, 0, true>(in, out, aux, w, b, F, fl, st, xm, wp, pout); \
-      return 1;                                                                                           \
-    }
+    if (!dg || up || b16 || (flags & (4 | 64))) return {};
+#define PAIG_CASE(CI, CO, HH, K)                      \
+    if (Cin == CI && Cout == CO && H == HH && ks == K) \
+      return {&sfwd_launch<CI, CO, HH, HH, K, true, false, 0, true>, 7 | 64};
     PAIG_SPLIT_UPT(PAIG_CASE)
 #undef PAIG_CASE
-    return 0;
+    return {};
   }
-  if (up) {
-    if (dg) return 0;
-#define PAIG_CASE(CI, CO, HH, K)                                                                          \
-    if (Cin == CI && Cout == CO && H == HH && ks == K) {                                                  \
-      *rc = b16 ? sfwd_launch<CI, CO, HH, HH, K, false, true, 2>(in, out, aux, w, b, F, fl, st, xm, wp, pout)           \
-                : sfwd_launch<CI, CO, HH, HH, K, false, true, 0>(in, out, aux, w, b, F, fl, st, xm, wp, pout);          \
-      return 1;                                                                                           \
-    }
+  if (up) {   // (an upsample tiling never pools)
+    if (dg) return {};
+#define PAIG_CASE(CI, CO, HH, K)                                                      \
+    if (Cin == CI && Cout == CO && H == HH && ks == K)                                 \
+      return {b16 ? &sfwd_launch<CI, CO, HH, HH, K, false, true, 2>                     \
+                  : &sfwd_launch<CI, CO, HH, HH, K, false, true, 0>, 7 | 64, pool};
     PAIG_SPLIT_UP(PAIG_CASE)
 #undef PAIG_CASE
-    return 0;
+    return {};
   }
-#define PAIG_CASE(CI, CO, HH, K)                                                                            \
-  if (Cin == CI && Cout == CO && H == HH && ks == K) {                                                      \
-    if (b16)                                                                                                \
-      *rc = dg ? sfwd_launch<CI, CO, HH, HH, K, true, false, 2>(in, out, aux, w, b, F, fl, st, xm, wp, pout)              \
-               : sfwd_launch<CI, CO, HH, HH, K, false, false, 2>(in, out, aux, w, b, F, fl, st, xm, wp, pout);            \
-    else                                                                                                    \
-      *rc = dg ? sfwd_launch<CI, CO, HH, HH, K, true, false, 0>(in, out, aux, w, b, F, fl, st, xm, wp, pout)              \
-               : sfwd_launch<CI, CO, HH, HH, K, false, false, 0>(in, out, aux, w, b, F, fl, st, xm, wp, pout);            \
-    return 1;                                                                                               \
+#define PAIG_CASE(CI, CO, HH, K)                                                              \
+  if (Cin == CI && Cout == CO && H == HH && ks == K) {                                       \
+    if (b16)                                                                                 \
+      return {dg ? &sfwd_launch<CI, CO, HH, HH, K, true, false, 2>                            \
+                 : &sfwd_launch<CI, CO, HH, HH, K, false, false, 2>, 7 | 64,                  \
+              pool && !SFwdCfg<CI, CO, HH, HH, K, false, 2>::POOLOK};                         \
+    return {dg ? &sfwd_launch<CI, CO, HH, HH, K, true, false, 0>                              \
+               : &sfwd_launch<CI, CO, HH, HH, K, false, false, 0>, 7 | 64,                    \
+            pool && !SFwdCfg<CI, CO, HH, HH, K, false, 0>::POOLOK};                           \
   }
   PAIG_SPLIT_FWD(PAIG_CASE)
 #undef PAIG_CASE
-  return 0;
+  return {};
 }
 
-int paig_conv_split_wgrad(FView x, FView dy, float* slab, int nblk_max, int* nblk_out, int F, int Cin, int Cout,
-                          int H, int W, int ks, int flags, hipStream_t st, int* rc, XMax xm, PoolOut pin) {
+static SWgFn swg_resolve(int Cin, int Cout, int H, int W, int ks, int flags) {
   const bool up = (flags & 32) != 0, b16 = (flags & 256) != 0;
-  if (H != W || !(flags & (128 | 256))) return 0;
-  if (x.grp > 0 && H * W < 256) return 0;   // multi-frame tiles step frames by a plain stride
+  if (H != W || !(flags & (128 | 256))) return nullptr;
   if (flags & 64) {   // the 2x2 max pool of the layer's output folded into the dY staging
-    if (up || b16) return 0;
-#define PAIG_CASE(CI, CO, HH, K)                                                                          \
-    if (Cin == CI && Cout == CO && H == HH && ks == K) {                                                  \
-      *rc = swg_launch<CI, CO, HH, HH, K, false, 0, true>(x, dy, slab, nblk_max, nblk_out, F, st, xm, pin);  \
-      return 1;                                                                                           \
-    }
+    if (up || b16) return nullptr;
+#define PAIG_CASE(CI, CO, HH, K) \
+    if (Cin == CI && Cout == CO && H == HH && ks == K) return &swg_launch<CI, CO, HH, HH, K, false, 0, true>;
     PAIG_SPLIT_PF(PAIG_CASE)
 #undef PAIG_CASE
-    return 0;
+    return nullptr;
   }
   if (up) {
-#define PAIG_CASE(CI, CO, HH, K)                                                                          \
-    if (Cin == CI && Cout == CO && H == HH && ks == K) {                                                  \
-      *rc = b16 ? swg_launch<CI, CO, HH, HH, K, true, 2>(x, dy, slab, nblk_max, nblk_out, F, st, xm)          \
-                : swg_launch<CI, CO, HH, HH, K, true, 0>(x, dy, slab, nblk_max, nblk_out, F, st, xm);         \
-      return 1;                                                                                           \
-    }
+#define PAIG_CASE(CI, CO, HH, K)                      \
+    if (Cin == CI && Cout == CO && H == HH && ks == K) \
+      return b16 ? &swg_launch<CI, CO, HH, HH, K, true, 2> : &swg_launch<CI, CO, HH, HH, K, true, 0>;
     PAIG_SPLIT_UP(PAIG_CASE)
 #undef PAIG_CASE
-    return 0;
+    return nullptr;
   }
-#define PAIG_CASE(CI, CO, HH, K)                                                                          \
-  if (Cin == CI && Cout == CO && H == HH && ks == K) {                                                    \
-    *rc = b16 ? swg_launch<CI, CO, HH, HH, K, false, 2>(x, dy, slab, nblk_max, nblk_out, F, st, xm)           \
-              : swg_launch<CI, CO, HH, HH, K, false, 0>(x, dy, slab, nblk_max, nblk_out, F, st, xm);          \
-    return 1;                                                                                             \
-  }
+#define PAIG_CASE(CI, CO, HH, K)                      \
+  if (Cin == CI && Cout == CO && H == HH && ks == K) \
+    return b16 ? &swg_launch<CI, CO, HH, HH, K, false, 2> : &swg_launch<CI, CO, HH, HH, K, false, 0>;
   PAIG_SPLIT_WG(PAIG_CASE)
 #undef PAIG_CASE
-  return 0;
+  return nullptr;
 }
 
-// 1 if paig_conv_split_fwd (what 0) / paig_conv_split_wgrad (what 1) has the shape
-int paig_conv_split_supported(int what, int Cin, int Cout, int H, int W, int ks, int flags) {
-  if (H != W) return 0;
-  const bool up = (flags & 32) != 0, dg = (flags & 8) != 0;
-  if ((flags & 64) && (what == 1 || dg)) {   // the output max pool's backward folded (wgrad / dgrad staging)
-    if (up || !(flags & 128) || (flags & (256 | 512))) return 0;
-#define PAIG_CASE(CI, CO, HH, K)                                                                         \
-    if (what == 1 ? (Cin == CI && Cout == CO) : (Cin == CO && Cout == CI)) {                             \
-      if (H == HH && ks == K) return 1;                                                                  \
-    }
-    PAIG_SPLIT_PF(PAIG_CASE)
-#undef PAIG_CASE
-    return 0;
-  }
-  if (flags & 64) {   // forward with the fused 2x2 max pool of its output
-    if (what != 0 || up || dg || !(flags & (128 | 256))) return 0;
-    const bool b16 = (flags & 256) != 0;
-#define PAIG_CASE(CI, CO, HH, K)                                                                         \
-    if (Cin == CI && Cout == CO && H == HH && ks == K)                                                   \
-      return b16 ? SFwdCfg<CI, CO, HH, HH, K, false, 2>::POOLOK : SFwdCfg<CI, CO, HH, HH, K, false, 0>::POOLOK;
-    PAIG_SPLIT_FWD(PAIG_CASE)
-#undef PAIG_CASE
-    return 0;
-  }
-#define PAIG_CASE(CI, CO, HH, K) \
-  if (Cin == CI && Cout == CO && H == HH && ks == K) return 1;
-  if (flags & 512) {
-    if (what != 0 || !dg || up || (flags & (4 | 64 | 256)) || !(flags & 128)) return 0;
-    PAIG_SPLIT_UPT(PAIG_CASE)
-    return 0;
-  }
-  if (up) {
-    if (dg) return 0;
-    PAIG_SPLIT_UP(PAIG_CASE)
-    return 0;
-  }
-  if (what == 0) {
-    PAIG_SPLIT_FWD(PAIG_CASE)
-  } else {
-    PAIG_SPLIT_WG(PAIG_CASE)
-  }
-#undef PAIG_CASE
-  return 0;
+}  // namespace
+
+int paig_conv_split_fwd(const ConvFwdOps* o, int Cin, int Cout, int H, int W, int ks, int flags, int* rc) {
+  const SFwdRoute r = sfwd_resolve(Cin, Cout, H, W, ks, flags);
+  if (!o) return r.launch && !r.nopool;
+  if (!r.launch) return 0;
+  if (o->in.grp > 0 && H * W < 256) return 0;   // multi-frame tiles step frames by a plain stride
+  *rc = r.launch(o->in, o->out, o->aux, o->w, o->b, o->F, flags & r.mask, o->st, o->xm, o->wp, o->pout);
+  return 1;
+}
+
+int paig_conv_split_wgrad(const ConvWgOps* o, int Cin, int Cout, int H, int W, int ks, int flags, int* rc) {
+  const SWgFn launch = swg_resolve(Cin, Cout, H, W, ks, flags);
+  if (!o || !launch) return launch != nullptr;
+  if (o->x.grp > 0 && H * W < 256) return 0;   // multi-frame tiles step frames by a plain stride
+  *rc = launch(o->x, o->dy, o->slab, o->nblk_max, o->nblk_out, o->F, o->st, o->xm, o->pin);
+  return 1;
 }
 
 void paig_conv_fwd_prezero(float* z, int zn) {
